@@ -9,7 +9,9 @@ steps per scene) -> slhip_synth_place (camera, light, shadow matrix, draw record
 the step's exchange shard.  Resident in HBM before the timed region: the asset table (mesh pool,
 textures, hulls of the 21 classes).  Everything per scene happens inside the timed region.
 
-Prints ONE JSON line (rank 0) -- see the repository brief for the contract."""
+Prints ONE JSON line (rank 0) -- see the repository brief for the contract.  A plain run does only what that line's headline
+figure needs; --full adds the rest (breakdowns, rooflines, capacities, exchange, CPU baseline, the other configurations).
+--dump-outputs DIR writes what the last timed step computed, for comparing two builds output for output."""
 import argparse
 import ctypes as C
 import json
@@ -28,6 +30,8 @@ RESOLUTION = (640, 480)
 INTRINSICS = (1066.778, 1067.487, 312.9869, 241.3109)  # reference examples/ycb.py:32
 N_OBJECTS = 20
 TARGET_RING = int(os.environ.get("SLHIP_BENCH_TARGET_RING", 4))     # render-target sets kept alive (chunks of --render-chunk scenes): 4 x 1024 scenes = 50 GB
+# --dump-outputs: 3 scenes of 640x480 ground truth are 52 MB in float32, the poses of 1024 scenes 1.4 MB -- under the 64 MB a dump may take
+DUMP_SEED, DUMP_GT_SCENES, DUMP_POSE_SCENES, DUMP_MAX_BYTES = 20261016, 3, 1024, 64 * 10**6
 
 
 def parse():
@@ -74,7 +78,16 @@ def parse():
                          "(shipped fixture, the default), native = the in-tree decomposition (stillleben_amd/acd.py over the quick-hull of "
                          "libslhip.so): row S1 of SURVEY 8a feeding the measured number")
     ap.add_argument("--no-ssao", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: per-phase and per-kernel timings and the rooflines priced on them, one "
+                         "isolated render and one settle alone after the timed region, the list-capacity read-out, the exchange "
+                         "measurement (N > 1), the CPU baseline and the other --config lines.  Without it a run sets up, warms up, "
+                         "times the --steps steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; the scene "
+                         "indices float64): the 6-channel ground truth of %d scenes of its last render chunk and the settled object "
+                         "and camera poses of %d of its scenes, both chosen by a fixed seed" % (DUMP_GT_SCENES, DUMP_POSE_SCENES))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
     ap.add_argument("--cpu-scenes", type=int, default=2, help="scenes per host thread of the bounded CPU-baseline sample")
     return ap.parse_args()
 
@@ -208,6 +221,7 @@ class Pipeline:
             done.record()
             self.free[k % self.ring] = done
         rec["render_events"] = revs
+        rec["last_chunk"] = buf       # the ground truth of the step's last chunk (a short last chunk gets buffers of its own)
         return rec
 
     def drain(self):
@@ -434,7 +448,13 @@ def run_other_config(args):
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if args.config != "C2":
+        if not args.full:
+            sys.exit("bench.py: --config %s is one of the other configurations: they run with --full" % args.config)
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs writes the headline workload's outputs (--config C2)")
         if args.gpus != 1:
             sys.exit("bench.py: --config %s is a single-GPU configuration" % args.config)
         return run_other_config(args)
@@ -477,8 +497,9 @@ def main():
     args.render_chunk = min(args.render_chunk, args.batch)
     pipe = Pipeline(sl, table, args.batch, args.render_chunk, not args.no_ssao, max(1, args.settle_streams), seed=20260929, rank=rank,
                     render_streams=min(max(1, args.render_streams), 2), pair_contact_budget=args.pair_budget)
-    pipe.eng.L.slhip_timing_enable(1)
-    pipe.eng.L.slhip_settle_timing_enable(1)
+    if args.full:     # HIP events around the render phases and the lockstep kernels inside the timed region: --full figures only
+        pipe.eng.L.slhip_timing_enable(1)
+        pipe.eng.L.slhip_settle_timing_enable(1)
     table.device()
     pipe.eng.pool_abi()
     torch.cuda.synchronize()
@@ -522,8 +543,9 @@ def main():
         return recs
 
     run(0, args.warmup)
-    pipe.eng.L.slhip_render_timings(C.byref((C.c_float * 8)()))   # drop warm-up phase timings
-    pipe.eng.L.slhip_settle_timings(C.byref((C.c_float * 5)()), C.byref((C.c_uint32 * 5)()))
+    if args.full:
+        pipe.eng.L.slhip_render_timings(C.byref((C.c_float * 8)()))   # drop warm-up phase timings
+        pipe.eng.L.slhip_settle_timings(C.byref((C.c_float * 5)()), C.byref((C.c_uint32 * 5)()))
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -552,6 +574,14 @@ def main():
             r["batch"].check_settled()     # a scene the kernel refused (sizing hints) or a list that overflowed must not pass silently ...
         except RuntimeError as e:          # ... nor take the measurement with it: the line reports it (caps, settle_errors)
             settle_errors.append(str(e)[:400])
+    if args.dump_outputs and rank == 0:   # before the --full legs below re-stage the last step's record set
+        dump_outputs(args.dump_outputs, recs[-1])
+    if not args.full:
+        out = None
+        if rank == 0:
+            out = headline(args, world, elapsed, table, pipe)
+            out["settle_errors"] = settle_errors
+        return finish(out, comm, dist)
 
     # phase timings: the render events of all timed steps accumulate in the library
     ms_all = (C.c_float * 8)()
@@ -673,6 +703,10 @@ def main():
         out["exchange"] = exchange
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(meshes, args.cpu_scenes, not args.no_ssao, args.pair_budget)
+    finish(out, comm, dist)
+
+
+def finish(out, comm, dist):
     if comm is not None:
         comm.close()
     if dist is not None:
@@ -731,7 +765,6 @@ def report(args, world, elapsed, table, pipe, t_settle, t_settle_alone, t_stage,
            settle_kernels, caps=None):
     W, H = RESOLUTION
     P = W * H
-    total_scenes = args.batch * world * args.steps
     n_chunks = (args.batch + args.render_chunk - 1) // args.render_chunk
     names = ["shadow_raster", "shadow_large", "vis_raster", "vis_large", "shade", "ssao", "ssao_apply", "tonemap"]
     cnt = load_counters()
@@ -855,25 +888,8 @@ def report(args, world, elapsed, table, pipe, t_settle, t_settle_alone, t_stage,
             roofline["achieved_alone"] = valu_per_launch * args.batch / (ms_alone * 1e-3) / 1e9
             roofline["frac_alone"] = roofline["achieved_alone"] / issue_peak
     k_dom = int(np.argmax(phases)) if phases.sum() > 0 else 4
-    return {
-        "metric": "scenes/sec (settle + 640x480 6-ch GT render), 20-obj YCB-like",
-        "value": total_scenes / elapsed, "unit": "scenes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {
-            "workload": "C2: 20 of 21 procedural YCB-like objects (8k verts/16k tris, 1024^2 texture each) per scene; per step and GPU "
-                        "%d scenes are staged (random stack), settled (100 frames x 4 substeps), framed (camera, light, shadow "
-                        "matrix) and rendered at 640x480 (rgb, coord+depth, class, instance, normals; shadows on, SSAO %s) -- "
-                        "all four stages inside the timed region" % (args.batch, "off" if args.no_ssao else "on"),
-            "scenes_per_gpu_per_step": args.batch, "render_chunk": args.render_chunk, "resolution": list(RESOLUTION),
-            "objects": N_OBJECTS, "settle_streams": len(pipe.s_settle), "render_streams": len(pipe.s_render_all),
-            "collision_hulls": ("the reference's V-HACD on this geometry (shipped fixture)" if args.hulls == "vhacd" else
-                                "the in-tree decomposition (acd.py + slhip_host_convex_hull)") + ": %d hulls in the 21 classes" % int(sum(table.n_hulls)),
-            "pair_contact_budget": caps["pair_contact_budget"] if caps else None,   # (slhip.h; 0 = every contact point, as in PhysX)
-            "parallelism": ("scenes sharded by rank, no data-path collective; exchange: RCCL all-gather of a %d-scene C3 shard per "
-                            "rank and step (%.0f MB per rank) -- %d of the %d scenes a rank renders per step are exchanged"
-                            % (pipe.gather_scenes, pipe.gather_scenes * P * 40 / 1e6, pipe.gather_scenes, args.batch)) if world > 1 else "1 GPU",
-        },
+    out = headline(args, world, elapsed, table, pipe)
+    out.update({
         "roofline": roofline,
         "roofline_render": roof_render,
         "breakdown_ms": {
@@ -886,7 +902,69 @@ def report(args, world, elapsed, table, pipe, t_settle, t_settle_alone, t_stage,
         # what the rank holds in HBM at its peak (torch's allocator: records, settle scratch, render scratch, the ring of ground truth)
         "hbm_footprint_GB": {"peak_allocated": torch.cuda.max_memory_allocated() / 1e9,
                              "device_total": torch.cuda.get_device_properties(torch.cuda.current_device()).total_memory / 1e9},
+    })
+    return out
+
+
+def headline(args, world, elapsed, table, pipe):
+    """The line's headline figure and the workload it was measured on: all that a run without --full prints."""
+    P = RESOLUTION[0] * RESOLUTION[1]
+    return {
+        "metric": "scenes/sec (settle + 640x480 6-ch GT render), 20-obj YCB-like",
+        "value": args.batch * world * args.steps / elapsed, "unit": "scenes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {
+            "workload": "C2: 20 of 21 procedural YCB-like objects (8k verts/16k tris, 1024^2 texture each) per scene; per step and GPU "
+                        "%d scenes are staged (random stack), settled (100 frames x 4 substeps), framed (camera, light, shadow "
+                        "matrix) and rendered at 640x480 (rgb, coord+depth, class, instance, normals; shadows on, SSAO %s) -- "
+                        "all four stages inside the timed region" % (args.batch, "off" if args.no_ssao else "on"),
+            "scenes_per_gpu_per_step": args.batch, "render_chunk": args.render_chunk, "resolution": list(RESOLUTION),
+            "objects": N_OBJECTS, "settle_streams": len(pipe.s_settle), "render_streams": len(pipe.s_render_all),
+            "collision_hulls": ("the reference's V-HACD on this geometry (shipped fixture)" if args.hulls == "vhacd" else
+                                "the in-tree decomposition (acd.py + slhip_host_convex_hull)") + ": %d hulls in the 21 classes" % int(sum(table.n_hulls)),
+            "pair_contact_budget": int(pipe.sets[0].settle_params["pair_contact_budget"]),   # (slhip.h; 0 = every contact point, as in PhysX)
+            "parallelism": ("scenes sharded by rank, no data-path collective; exchange: RCCL all-gather of a %d-scene C3 shard per "
+                            "rank and step (%.0f MB per rank) -- %d of the %d scenes a rank renders per step are exchanged"
+                            % (pipe.gather_scenes, pipe.gather_scenes * P * 40 / 1e6, pipe.gather_scenes, args.batch)) if world > 1 else "1 GPU",
+        },
     }
+
+
+def dump_outputs(dirname, rec):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files -- the 6-channel ground truth of DUMP_GT_SCENES
+    scenes of its last render chunk (the earlier chunks' targets have been re-used by then) and the settled object poses and
+    camera poses of DUMP_POSE_SCENES of its scenes, both picked by DUMP_SEED.  Values are converted to float32 exactly."""
+    from stillleben_amd import _abi
+    from stillleben_amd import _settle_batch as SB
+
+    b, buf = rec["batch"], rec["last_chunk"]
+    rng = np.random.default_rng(DUMP_SEED)
+    gt = np.sort(rng.choice(buf.B, size=min(DUMP_GT_SCENES, buf.B), replace=False))
+    scenes = np.sort(rng.choice(b.n_scenes, size=min(DUMP_POSE_SCENES, b.n_scenes), replace=False))
+    out = {"gt_scene_index": ((b.n_render_chunks() - 1) * b.render_chunk + gt).astype(np.float64),
+           "pose_scene_index": scenes.astype(np.float64)}
+    idx = torch.from_numpy(gt).to(buf.rgb.device)
+    for name, t in (("rgb", buf.rgb), ("coord_depth", buf.coord), ("class_index", buf.cls), ("instance_index", buf.instance),
+                    ("normals", buf.normals)):
+        if t is not None:
+            out[name] = t.index_select(0, idx).float().cpu().numpy()
+
+    def records(d, dtype, per_scene):       # the picked scenes' records of a device array of per-scene record groups
+        rows = d[:b.n_scenes * per_scene * dtype.itemsize].view(b.n_scenes, per_scene * dtype.itemsize)
+        host = rows.index_select(0, torch.from_numpy(scenes).to(d.device)).cpu().numpy()
+        return np.frombuffer(host.tobytes(), dtype=dtype)
+
+    bodies = records(b.d_bodies, SB.BODY_DTYPE, b.n_objects)
+    out["object_poses"] = bodies["pose"].astype(np.float32).reshape(len(scenes), b.n_objects, 4, 4)
+    synth = records(b.d_scenes, _abi.SYNTH_SCENE_DTYPE, 1)
+    out["camera_poses"] = synth["camera_pose"].astype(np.float32).reshape(len(scenes), 4, 4)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("bench.py: --dump-outputs would write %d bytes (at most %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 if __name__ == "__main__":

@@ -22,7 +22,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BENCH = ["python", os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"]
+BENCH = ["python", os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"]   # --full: the line carries the per-kernel timings
 PMC_SHAPE = ["--steps", "1", "--warmup", "0", "--settle-streams", "1", "--render-streams", "1"]   # one step: every kernel of the path once, serialised
 N_CAL = 1 << 31
 
@@ -144,8 +144,8 @@ def main():
     res = {
         "kernel_source_sha": bench.kernel_source_sha(),     # bench.py quotes per-instruction figures only for THESE sources
         "commands": {
-            "stats": "rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --no-cpu-baseline",
-            "pmc": "rocprofv3 --pmc <FETCH_SIZE | WRITE_SIZE | SQ_...> --kernel-trace --output-format csv -- python bench.py --no-cpu-baseline " + " ".join(PMC_SHAPE),
+            "stats": "rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --no-cpu-baseline",
+            "pmc": "rocprofv3 --pmc <FETCH_SIZE | WRITE_SIZE | SQ_...> --kernel-trace --output-format csv -- python bench.py --full --no-cpu-baseline " + " ".join(PMC_SHAPE),
             "calibration": "same two --pmc passes over python tools/pmc_calibrate.py (2 GiB read + 2 GiB written per dispatch, 16 B per lane)",
         },
         "shape": {"scenes_per_settle_launch": batch, "scenes_per_render_launch": chunk},

@@ -41,7 +41,9 @@ extern "C" {
                                  4: slhip_settle_params.max_body_pairs_per_scene (120 bytes); slhip_settle_caps fills ten counts
                                  5: slhip_settle_params.stabilization_threshold (128 bytes); slhip_body.stab (304 bytes) carries the
                                     stabilisation state of a body, SLHIP_BODY_FROZEN; slhip_settle_solver_wave_lds, slhip_host_convex_hull,
-                                    slhip_host_fill_holes                                                                      */
+                                    slhip_host_fill_holes
+                                 5, additive (no struct or signature changed; detect with dlsym): slhip_object_stats,
+                                    slhip_render_object_stats, slhip_render_object_stats_bytes                                 */
 #define SLHIP_NUM_LIGHTS 3 /* reference include/stillleben/common.h:17 */
 
 /* ---------------------------------------------------------------------------------------------
@@ -275,6 +277,49 @@ int slhip_render_ssao_skipped(const slhip_render_scratch* scratch, uint32_t n_sc
 int slhip_render_scratch_bytes(uint32_t n_scenes, uint32_t width, uint32_t height,
                                uint32_t shadow_res, uint32_t queue_capacity,
                                uint64_t bytes_out[7]);   /* vis, hdr, ao, shadow, queue, lum, shadow_tiles */
+
+/* Per-object visibility statistics of a render: for every scene and slot, the numbers of the BOP toolkit's scene_gt_info.
+ * Slot i is instance index i (instance_index & 0xFFFF, what the instance output shows; draws that share an index share a slot);
+ * slot 0 -- the background plane and other unindexed draws -- is always empty, as is a slot without draws.
+ *   px_visib, bbox_visib: the pixels whose instance output is i, and their box;
+ *   px_all, bbox_obj:     the pixels the visibility pass covers with slot i's draws drawn alone (no other draw, no plane; same
+ *                         viewport, camera, fill rule, near clipping, depth-range rules and alpha test), and their box.
+ * Boxes are (x, y, w, h) with (x, y) the top-left pixel; an empty box is (-1, -1, -1, -1).  All values are integers computed with
+ * integer atomics: bit-exact and the same from run to run.  visib_fract = px_visib / px_all (0 when px_all == 0) is left to
+ * the caller.  40 bytes. */
+typedef struct {
+    uint32_t px_visib, px_all;
+    int32_t  bbox_visib[4];
+    int32_t  bbox_obj[4];
+} slhip_object_stats;
+
+#define SLHIP_OBJECT_STATS_CAPACITY 1   /* status of slhip_render_object_stats: the word pool is too small (see below) */
+
+/* Worst-case size of the word pool of slhip_render_object_stats: one u64 word per 8 x 8-pixel tile of the viewport for every
+ * scene and slot 1..n_slots-1, n_scenes * (n_slots - 1) * ceil(W / 8) * ceil(H / 8).  A call needs one word per tile of each
+ * slot's screen box only (the box of its vertices; the whole viewport for a slot with a vertex behind the near plane), usually
+ * far less.  Host only.                                                                                                        */
+int slhip_render_object_stats_bytes(uint32_t n_scenes, uint32_t n_slots, uint32_t width, uint32_t height,
+                                    uint64_t* worst_case_words);
+
+/* Statistics of the slhip_render that preceded this call on the same stream.  pool, d_scenes, d_draws, d_chunks, n_scenes,
+ * n_draws, n_chunks, width and height are the arguments that render consumed, and `scratch` its scratch: the visibility keys
+ * (d_vis), the vertex caches (d_clip, d_vattr) are read, the queue (d_queue, queue_capacity) is reused.  PRECONDITION: nothing
+ * touches that scratch between the two calls.  A render with a depth-peel input has no single "whole silhouette": its
+ * statistics describe the unpeeled draws, and callers should not ask for them.
+ *   n_slots   slots per scene (the largest instance index of the batch + 1; draws with a larger index are not counted)
+ *   d_words   u64 working pool of capacity_words words (device)
+ *   d_out     slhip_object_stats [n_scenes][n_slots] (device); also the working space of the call
+ *   words_needed  (host, may be NULL) the words this batch needs
+ * Returns 0, SLHIP_OBJECT_STATS_CAPACITY when capacity_words < *words_needed (no statistics are written; d_out holds working
+ * values; grow the pool and call again -- the render's outputs stay valid), or a negative error (slhip_last_error).
+ * Synchronises `stream` once (the pool size is known after the first pass).                                                    */
+int slhip_render_object_stats(const slhip_mesh_pool* pool,
+                              const slhip_scene* d_scenes, const slhip_draw* d_draws,
+                              const slhip_chunk* d_chunks, uint32_t n_scenes, uint32_t n_draws, uint32_t n_chunks,
+                              uint32_t width, uint32_t height, const slhip_render_scratch* scratch,
+                              uint32_t n_slots, uint64_t* d_words, uint64_t capacity_words,
+                              slhip_object_stats* d_out, uint64_t* words_needed, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Settle half (replaces PhysX as driven by Scene::simulateTableTopScene, scene.cpp:612-759)

@@ -39,6 +39,7 @@ RENDER_SSAO = 0x100
 RENDER_SHADOWS = 0x200
 RENDER_SHADOW_RESET = 0x400
 RENDER_KEEP_HDR = 0x800
+OBJECT_STATS_CAPACITY = 1     # SLHIP_OBJECT_STATS_CAPACITY: status of slhip_render_object_stats when the word pool is too small
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
 COMM_ID_BYTES = 128
@@ -139,6 +140,11 @@ assert SCENE_DTYPE.itemsize == 480, SCENE_DTYPE.itemsize
 CHUNK_DTYPE = np.dtype(
     [("scene", np.uint32), ("draw", np.uint32), ("first_tri", np.uint32), ("count", np.uint32)]
 )
+
+# slhip_object_stats (include/slhip.h): per (scene, slot) visibility statistics, 40 bytes
+OBJECT_STATS_DTYPE = np.dtype([("px_visib", np.uint32), ("px_all", np.uint32), ("bbox_visib", np.int32, (4,)),
+                               ("bbox_obj", np.int32, (4,))])
+assert OBJECT_STATS_DTYPE.itemsize == 40, OBJECT_STATS_DTYPE.itemsize
 
 # slhip_host_object / slhip_host_scene (include/slhip.h): flat descriptors for the C++ record assembly
 HOST_OBJECT_DTYPE = np.dtype([
@@ -275,6 +281,11 @@ def lib():
     L.slhip_records_count.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.slhip_records_build_render.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                              C.c_uint32, C.c_void_p, C.c_uint32]
+    L.slhip_render_object_stats.argtypes = [
+        C.POINTER(MeshPool), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+        C.POINTER(RenderScratch), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p,
+    ]
+    L.slhip_render_object_stats_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.slhip_render_ssao_skipped.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64 * 2), C.c_void_p]
     L.slhip_settle_caps.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64 * 10), C.c_void_p]
     L.slhip_settle_timing_enable.argtypes = [C.c_int]

@@ -33,6 +33,7 @@ class RenderBuffers:
         self.vertex_idx = mk(_abi.OUT_VERTEX_IDX, (B, H, W, 4), torch.int32)
         self.bary = mk(_abi.OUT_BARY, (B, H, W, 4), torch.float32)
         self.cam_coord = mk(_abi.OUT_CAM_COORD, (B, H, W, 4), torch.float32)
+        self.object_stats = None   # ObjectStats of the last render into these buffers, when it was asked for
 
     def abi(self):
         o = _abi.RenderOut()
@@ -140,33 +141,54 @@ class Engine:
         return torch.from_numpy(raw.copy()).to(self.device)
 
     def render(self, scenes, mask=_abi.OUT_ALL, ssao=True, shadows=True, depth_peel=None, predicate=None,
-               buffers=None, keep_hdr=False):
+               buffers=None, keep_hdr=False, object_stats=False):
+        """`object_stats`: also compute the per-object visibility statistics (buffers.object_stats, an ObjectStats with one
+        slot per instance index up to the largest of the batch's objects -- filtered out by `predicate` or not).  Not with
+        `depth_peel`: a peeled layer has no single "whole silhouette" (ValueError)."""
         W, H = scenes[0]._viewport
         for s in scenes:
             if s._viewport != (W, H):
                 raise ValueError("all scenes of a batch must share one viewport")
+        if object_stats and depth_peel is not None:
+            raise ValueError("object_stats cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
+        n_slots = None
+        if object_stats:
+            n_slots = 1 + max((int(o.instance_index) for s in scenes for o in s._objects), default=0)
         want_rgb = bool(mask & _abi.OUT_RGB)
         srec, drec, crec = build_batch(scenes, self.pool, predicate, with_shadows=shadows and want_rgb)
-        return self.render_records(srec, drec, crec, W, H, mask, ssao, shadows, depth_peel, buffers, keep_hdr)
+        return self.render_records(srec, drec, crec, W, H, mask, ssao, shadows, depth_peel, buffers, keep_hdr,
+                                   object_stats=object_stats, n_slots=n_slots)
 
     def render_records(self, srec, drec, crec, W, H, mask=_abi.OUT_ALL, ssao=True, shadows=True, depth_peel=None,
-                       buffers=None, keep_hdr=False):
-        """Renders a batch described by prebuilt slhip_scene / slhip_draw / slhip_chunk records (host arrays)."""
+                       buffers=None, keep_hdr=False, object_stats=False, n_slots=None, stats_capacity=None):
+        """Renders a batch described by prebuilt slhip_scene / slhip_draw / slhip_chunk records (host arrays).  With
+        `object_stats` and no `n_slots`: one slot per instance index up to the largest of the draws."""
+        if object_stats and n_slots is None:
+            n_slots = 1 + (int((drec["instance_index"] & 0xFFFF).max()) if len(drec) else 0)
         d_s, d_d, d_c = self.upload_records(srec), self.upload_records(drec), self.upload_records(crec)
         n_clip = int(drec["n_verts"].sum()) if len(drec) else 0
         # shadow maps for the lights the batch uses (a light with zero colour or direction is off: light_active() of the kernels)
         on = (np.abs(srec["light_color"][:, :, :3]).sum(axis=2) > 0) & (np.abs(srec["light_dir"][:, :, :3]).sum(axis=2) > 0)
         lights = max(1, int(np.max(np.nonzero(on.any(axis=0))[0]) + 1)) if on.any() else 1
         buffers = self.render_device(d_s, d_d, d_c, len(srec), len(drec), len(crec), n_clip, W, H, mask, ssao, shadows,
-                                     depth_peel, buffers, keep_hdr, shadow_lights=lights)
+                                     depth_peel, buffers, keep_hdr, shadow_lights=lights, object_stats=object_stats,
+                                     n_slots=n_slots, stats_capacity=stats_capacity)
         buffers._keepalive += (d_s, d_d, d_c)   # alive until the stream has consumed them
         return buffers
 
     def render_device(self, d_s, d_d, d_c, B, n_draws, n_chunks, n_clip, W, H, mask=_abi.OUT_ALL, ssao=True, shadows=True,
-                      depth_peel=None, buffers=None, keep_hdr=False, shadow_lights=_abi.NUM_LIGHTS):
+                      depth_peel=None, buffers=None, keep_hdr=False, shadow_lights=_abi.NUM_LIGHTS, object_stats=False,
+                      n_slots=None, stats_capacity=None):
         """slhip_render on records that already live in HBM (device tensors or raw device addresses):
         `n_clip` = clip-position slots the draws' clip_base + n_verts ranges span; `shadow_lights` = shadow maps per scene
-        (lights with a higher index cast no shadow)."""
+        (lights with a higher index cast no shadow).  `object_stats`: slhip_render_object_stats right after the render on the
+        same stream, with `n_slots` slots per scene (required) -> buffers.object_stats; not with `depth_peel` (ValueError).
+        `stats_capacity`: words of the stats pool to start from (tests; the pool grows as needed)."""
+        if object_stats:
+            if depth_peel is not None:
+                raise ValueError("object_stats cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
+            if n_slots is None or int(n_slots) < 1:
+                raise ValueError("object_stats needs n_slots (the largest instance index of the batch + 1)")
         want_rgb = bool(mask & _abi.OUT_RGB)
         ssao = ssao and want_rgb
         shadows = shadows and want_rgb
@@ -205,4 +227,34 @@ class Engine:
         _abi.check(st, "slhip_render")
         keep["shadow_ready"] = bool(shadows)
         buffers._keepalive = (keep,)
+        buffers.object_stats = None
+        if object_stats:
+            buffers.object_stats = self._object_stats(pool, addr(d_s), addr(d_d), addr(d_c), B, n_draws, n_chunks, W, H, scratch,
+                                                      int(n_slots), stream, stats_capacity)
         return buffers
+
+    def _object_stats(self, pool, d_s, d_d, d_c, B, n_draws, n_chunks, W, H, scratch, n_slots, stream, capacity=None):
+        """slhip_render_object_stats on the render just enqueued (same records, same scratch, same stream).  The word pool is
+        kept per stream; when it is too small it grows to what the call reports and only the stats call is repeated."""
+        from .object_stats import ObjectStats
+
+        out = torch.empty((B, n_slots, 10), dtype=torch.int32, device=self.device)
+        pools = self.__dict__.setdefault("_stats_words", {})
+        words = pools.get(stream)
+        if words is None or capacity is not None:
+            n0 = int(capacity) if capacity is not None else max(1 << 16, B * max(n_slots - 1, 1) * 256)
+            words = pools[stream] = torch.empty(max(n0, 1), dtype=torch.int64, device=self.device)
+        need = C.c_uint64(0)
+        self.last_stats_calls = []      # (status, capacity, words needed) of each call: the growth of the pool, for inspection
+        with torch.cuda.device(self.device):
+            for _ in range(3):
+                st = self.L.slhip_render_object_stats(C.byref(pool), d_s, d_d, d_c, B, n_draws, n_chunks, W, H, C.byref(scratch),
+                                                      n_slots, _ptr(words), words.numel(), _ptr(out), C.byref(need),
+                                                      C.c_void_p(stream))
+                self.last_stats_calls.append((st, words.numel(), int(need.value)))
+                if st != _abi.OBJECT_STATS_CAPACITY:
+                    break
+                words = pools[stream] = torch.empty(int(need.value) + int(need.value) // 4 + 1024, dtype=torch.int64,
+                                                    device=self.device)
+        _abi.check(st, "slhip_render_object_stats")
+        return ObjectStats.from_records(out)

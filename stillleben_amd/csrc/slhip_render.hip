@@ -2585,3 +2585,6 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
     mark(kNumPhases, stream);
     return 0;
 }
+
+// per-object visibility statistics (slhip_render_object_stats): kernels that reuse the raster core above
+#include "slhip_render_stats.inc"

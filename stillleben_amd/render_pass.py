@@ -56,6 +56,17 @@ class RenderPassResult:
     def cam_coordinates(self):
         return self._get("cam_coord")
 
+    def object_stats(self):
+        """Per-object visibility statistics of the rendered scene (sl.ObjectStats, tensors [S] / [S, 4]; slot i = instance
+        index i), computed when RenderPass.object_stats_enabled was set for the render.  Raises RuntimeError otherwise."""
+        if self._buffers is None:
+            raise RuntimeError("RenderPassResult is empty: render something first")
+        st = self._buffers.object_stats
+        if st is None:
+            raise RuntimeError("the last render did not compute object statistics (set RenderPass.object_stats_enabled)")
+        cuda = require_context().cuda_outputs
+        return st[self._index].map(lambda t: t.clone() if cuda else t.cpu())
+
 
 class RenderPass:
     def __init__(self, shading="pbr"):
@@ -64,17 +75,21 @@ class RenderPass:
             raise ValueError("unknown shading type specified")
         self._shading = shading  # stored, never read by the render path (quirk q2)
         self.ssao_enabled = True  # render_pass.h:150
+        self.object_stats_enabled = False   # additive: per-object visibility statistics (RenderPassResult.object_stats())
         self._result = RenderPassResult()
         self._buffers = None
 
     def render(self, scene, result=None, depth_peel=None, predicate=None):
+        """With object_stats_enabled, a `depth_peel` render raises ValueError: a peeled layer has no single whole silhouette."""
+        if self.object_stats_enabled and depth_peel is not None:
+            raise ValueError("object statistics cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
         res = result if result is not None else self._result
         peel = None
         if depth_peel is not None:
             peel = depth_peel._buffers.coord[depth_peel._index:depth_peel._index + 1].contiguous()
         own = res._buffers if (res._buffers is not None and res._buffers.B == 1 and res is not depth_peel) else None
         res._buffers = engine().render([scene], _abi.OUT_ALL, ssao=self.ssao_enabled, shadows=True,
-                                       depth_peel=peel, predicate=predicate, buffers=own)
+                                       depth_peel=peel, predicate=predicate, buffers=own, object_stats=self.object_stats_enabled)
         res._index = 0
         return res
 

@@ -280,8 +280,9 @@ class SceneBatch:
     def n_render_chunks(self):
         return (self.n_scenes + self.render_chunk - 1) // self.render_chunk
 
-    def render(self, chunk=0, mask=_abi.OUT_GT6, ssao=True, buffers=None):
-        """slhip_render of render chunk `chunk` (scenes [chunk * render_chunk, ...)) on the current stream."""
+    def render(self, chunk=0, mask=_abi.OUT_GT6, ssao=True, buffers=None, object_stats=False):
+        """slhip_render of render chunk `chunk` (scenes [chunk * render_chunk, ...)) on the current stream.  `object_stats`: also
+        the per-object visibility statistics (the returned buffers' .object_stats; slot i = object i - 1 of a scene)."""
         rc = self.render_chunk
         s0 = chunk * rc
         B = min(rc, self.n_scenes - s0)
@@ -295,11 +296,12 @@ class SceneBatch:
             self.d_drec.data_ptr() + s0 * md * _abi.DRAW_DTYPE.itemsize,
             self.d_crec.data_ptr() + s0 * mk * _abi.CHUNK_DTYPE.itemsize,
             B, B * md, B * mk, B * mv, W, H, mask, ssao=ssao, shadows=self.shadows, buffers=buffers,
-            shadow_lights=1)       # the synthesised scenes have one light (k_synth_place)
+            shadow_lights=1,       # the synthesised scenes have one light (k_synth_place)
+            object_stats=object_stats, n_slots=self.n_objects + 1)   # instance index = object + 1 (k_synth_place)
 
-    def render_chunks(self, mask=_abi.OUT_GT6, ssao=True):
+    def render_chunks(self, mask=_abi.OUT_GT6, ssao=True, object_stats=False):
         for c in range(self.n_render_chunks()):
-            yield self.render(c, mask, ssao)
+            yield self.render(c, mask, ssao, object_stats=object_stats)
 
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):

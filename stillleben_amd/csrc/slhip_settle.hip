@@ -1129,7 +1129,9 @@ __device__ void solve_group_lds(Contact* ac, int begin, int end, int ia, int ib,
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         { ROWP_STAMP(tr2); ROWP_ADD(0, 1); ROWP_ADD(1, tr1 - tr0); ROWP_ADD(2, tr2 - tr1); rows_cyc += tr2 - tr0; }
 #endif
-        if (!last) continue;
+        // (a patch that the list's capacity cut right behind its centre row -- p0 == end -- has no anchor: the centre's normal row
+        // alone, as the oracle's solve_patch with m == 0; nothing at or beyond `end` is touched)
+        if (!last || p0 > ci) continue;
         ROWP_STAMP(tf0);
         const int anchors = ci - p0 >= 1 ? 2 : 1;
         const float share = anchors == 2 ? 0.5f * nsum : nsum;
@@ -1235,7 +1237,10 @@ __device__ void solve_group(const ContactList ac, int begin, int end, int ia, in
     };
     while (ci < end) {
         nsum = 0.0f;
-        if (nxt.kt1 < 0.0f) normal_row(nullptr);          // the patch's centre row: first, never an anchor (three or four points follow)
+        if (nxt.kt1 < 0.0f) {                             // the patch's centre row: first, never an anchor (three or four points follow)
+            normal_row(nullptr);
+            if (!more) break;                             // ... unless the list's capacity cut them off: its normal row alone (oracle solve_patch, m == 0)
+        }
         const int p0 = ci;
         Anchor a0, a1;
         normal_row(&a0);

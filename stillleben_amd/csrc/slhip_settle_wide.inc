@@ -594,15 +594,17 @@ __device__ __forceinline__ int gjk_work_item(unsigned e_work, const float* __res
     // pair cache (oracle scene_ws.cache + pm): what the previous step left for this pair, if it listed the pair at all
     const int n_hulls = H->n_hulls;
     const int4* slot_p = pair_cache_slot(pc, s, n_hulls, la, lb, step - 1u, false);
-    bool prev_ok = false;
+    bool prev_ok = false, prev_filed = false;
     int prev_slot = 0;
     if (slot_p) {
         const int4 q = *slot_p;
         if (((unsigned)q.x >> 3) == ((step - 1u) & 0x1fffffffu)) {
             cached.n = q.x & 3; cached.i0 = sv_unpack(q.y & 0xffff); cached.i1 = sv_unpack((q.y >> 16) & 0xffff); cached.i2 = sv_unpack(q.z & 0xffff);
-            // the pair's manifold of the previous step, if that step left one with points in it
+            // the pair's manifold of the previous step, if that step filed one (its centre row's impulse is carried even when the
+            // list's capacity left it no point: oracle hull_pair_contacts, prev.lc), and whether it has points to refresh
             if (((q.x >> 2) & 1) != 0) {
                 prev_slot = (int)((unsigned)q.z >> 16);
+                prev_filed = true;
                 prev_ok = W.pm[((size_t)((step - 1u) & 1u) * n_scenes + s) * W.p_cap + prev_slot].count > 0;
             }
         }
@@ -629,7 +631,7 @@ __device__ __forceinline__ int gjk_work_item(unsigned e_work, const float* __res
                                   W.stage + ((size_t)s * W.p_cap + k) * 4, lost);
         }
         mr.type = lost ? 1 : 3;
-        mr.seed.n = prev_slot; mr.seed.i0 = prev_ok ? 1 : 0; mr.seed.i1 = no; mr.seed.i2 = 0;
+        mr.seed.n = prev_slot; mr.seed.i0 = prev_filed ? 1 : 0; mr.seed.i1 = no; mr.seed.i2 = 0;
     }
     W.mr[(size_t)s * W.p_cap + k] = mr;
     return mr.type;
@@ -1344,7 +1346,8 @@ __device__ __forceinline__ void finish_scene(char* smem, const int s, const unsi
                 }
             }
             if (lead && off < c_cap) {
-                // its impulse of the previous step: before the first point's in the step's impulse array, when that manifold had one
+                // its impulse of the previous step: before the first point's in the step's impulse array, when that step filed the
+                // pair's manifold with a centre row (with or without points behind it)
                 float carried = 0.0f;
                 if (mrs[k].seed.i0) {
                     const PM& pv = pm_prev[mrs[k].seed.n];

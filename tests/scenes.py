@@ -124,3 +124,61 @@ def sheet_scene(sl, mesh, roll_deg=17.0, tilt_deg=0.0, distance=4.0, size=(320, 
     obj.set_pose(torch.from_numpy((cam @ P).astype(np.float32)))
     scene.add_object(obj)
     return scene
+
+
+# ---- settle scenes whose solver list has a known row structure (tests of the per-scene list capacities) -------------------------
+# A cube face-down on the table or on another cube is a patch of four points behind its centre row: five rows in the list; a cube
+# on one of its edges is a patch of two points without a centre row.  The table's patches come first, in body order, then the
+# hull pairs'.  The sliders keep sliding for the first frames: a wrong friction row would change their velocities.
+CUT_TABLE = 0.04
+CUT_ROWS = {"sliders": 25, "edge": 17, "long": 40, "grid": 500, "row": 25}    # rows each of the first steps offers
+CUT_PAIRS = {"sliders": 1, "edge": 2, "long": 2, "grid": 0, "row": 2}          # hull pairs = touching body pairs (a cube is one hull)
+CUT_VELOCITY = (1.2, 0.6, 0.0)                                      # of the sliders of variant 0
+_cut_cube = {}
+
+
+def _cut_pose(x, y, z, yaw=0.0, roll=0.0):
+    cy, sy, cr, sr = math.cos(yaw), math.sin(yaw), math.cos(roll), math.sin(roll)
+    p = np.eye(4, dtype=np.float32)
+    p[:3, :3] = np.array([[cy, -sy, 0.0], [sy, cy, 0.0], [0.0, 0.0, 1.0]]) @ np.array([[1.0, 0.0, 0.0], [0.0, cr, -sr], [0.0, sr, cr]])
+    p[:3, 3] = (x, y, z)
+    return p
+
+
+def cut_scene(sl, kind, variant=0):
+    """kind "sliders": three yawed cubes sliding face-down on the table + a column of two (four table patches and one face patch,
+    five rows each: 25); "edge": a cube sliding on one edge (2 rows) + a column of three (5 + 2 x 5: 17); "long": five sliders + a
+    column of three (40); "grid": 100 sliders, 10 x 10 (500); "row": three cubes side by side on the table, sliding across the row
+    (three table patches and two side patches: 25; every body has a table group).  `variant` turns the yaws and the direction of
+    sliding: the same rows."""
+    if sl not in _cut_cube:
+        m = sl.Mesh(CUBE)
+        m.center_bbox()
+        m.scale_to_bbox_diagonal(0.2)
+        _cut_cube[sl] = m
+    h = 0.2 / math.sqrt(3.0) / 2.0
+    z0 = CUT_TABLE + h + 0.0015                                         # resting on the table (rest offset)
+    a = 0.7 * variant
+    v = CUT_VELOCITY if variant == 0 else (1.35 * math.cos(0.46 + a), 1.35 * math.sin(0.46 + a), 0.0)
+    items = []
+    if kind in ("sliders", "long"):
+        n = 3 if kind == "sliders" else 5
+        items += [(_cut_pose(-0.6 + 0.3 * k, 0.4, z0, yaw=0.3 + 0.25 * k + a), v) for k in range(n)]
+    if kind == "edge":
+        items.append((_cut_pose(-0.4, 0.0, CUT_TABLE + h * math.sqrt(2.0) + 0.0015, yaw=a, roll=math.pi / 4),
+                      (1.2 * math.cos(a), 1.2 * math.sin(a), 0.0)))                  # sliding along its edge
+    if kind == "row":
+        c, s_ = math.cos(a), math.sin(a)
+        items += [(_cut_pose(k * (2 * h + 0.001) * c, k * (2 * h + 0.001) * s_, z0, yaw=a), (-1.2 * s_, 1.2 * c, 0.0)) for k in (-1, 0, 1)]
+    if kind == "grid":
+        items += [(_cut_pose(0.3 * (i - 5), 0.3 * (j - 5), z0, yaw=0.1 + 0.05 * (10 * i + j) + a), v) for i in range(10) for j in range(10)]
+    column = {"sliders": 2, "edge": 3, "long": 3, "grid": 0, "row": 0}[kind]
+    items += [(_cut_pose(0.3, -0.3, z0 + k * (2 * h + 0.003), yaw=0.2 + a), None) for k in range(column)]
+    scene = sl.Scene((64, 48))
+    for p, vel in items:
+        o = sl.Object(_cut_cube[sl])
+        scene.add_object(o)
+        o.set_pose(torch.from_numpy(p))
+        if vel is not None:
+            o.linear_velocity = torch.tensor(vel, dtype=torch.float32)
+    return scene

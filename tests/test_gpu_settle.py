@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import scenes as S
+import test_oracle_settle as O
 from stillleben_amd import _settle_batch as SB
 
 pytestmark = pytest.mark.gpu
@@ -778,3 +779,160 @@ def test_manipulation_steps_equal_one_call(sl, oracle):
     assert np.array_equal(one["pose"].reshape(-1, 4, 4), np.stack([o._pose for o in scene._objects]))
     assert np.array_equal(one["lin_vel"][:, :3], np.stack([o._linear_velocity for o in scene._objects]))
     assert float(scene.objects[1].pose()[0, 3]) > 0.105      # the tool pushed its neighbour
+
+
+# ---- the per-scene contact list cut at every row (max_contacts_per_scene below what a step offers) ----------------------------
+# S.cut_scene builds scenes whose list has a known row structure: patches of four points behind a centre row (five rows), an edge
+# patch of two points.  The oracle's cut rule is pinned on the CPU (tests/test_oracle_settle.py); here the kernels must follow it
+# bit for bit wherever the cut lands -- on a centre row in particular, which leaves that patch its centre alone (no friction row).
+
+def _cut_batch(sl, kinds):
+    from stillleben_amd import physics
+
+    se = physics.settle_engine()
+    scs = [S.cut_scene(sl, k, v) for k, v in kinds]
+    srec, bodies = SB.build_settle_batch(scs, se.pool, [(True, S.CUT_TABLE)] * len(scs))
+    hulls, verts = se.pool.arrays()
+    return se, (srec, bodies, hulls, verts)
+
+
+def _cut_parity(se, oracle, batch, prm, what=""):
+    """ONE slhip_settle with exactly prm's capacities against the oracle: the bodies bit for bit, every counter identical."""
+    srec, bodies, hulls, verts = batch
+    gpu, caps = se.run_with_caps(srec, bodies.copy(), prm)
+    ref, oc = O.settle_with_caps(oracle, batch, prm)
+    try:
+        assert_bodies_equal(gpu, ref)
+        assert caps["contact_drop_steps"] == int(oc[:, 0].sum()), ("contact_drop_steps", caps, oc)
+        assert caps["pair_drop_steps"] == int(oc[:, 1].sum()), ("pair_drop_steps", caps, oc)
+        assert caps["group_drop_steps"] == int(oc[:, 5].sum()), ("group_drop_steps", caps, oc)
+        assert caps["max_contacts"] == int(oc[:, 2].max()) and caps["max_hull_pairs"] == int(oc[:, 3].max()), (caps, oc)
+        assert caps["contact_sum"] == int(oc[:, 6].astype(np.uint64).sum()), ("contact_sum", caps, oc)
+        assert caps["scenes_dropped"] == int((oc[:, [0, 1, 5]].sum(axis=1) > 0).sum()), ("scenes_dropped", caps, oc)
+    except AssertionError as e:
+        raise AssertionError("%s: %s" % (what, e)) from None
+    return gpu, caps
+
+
+@pytest.mark.parametrize("kind", ["sliders", "edge"])
+def test_contact_capacity_cut_at_every_row(sl, oracle, kind):
+    """max_contacts_per_scene from 1 to the offered count + 1 (pair_contact_budget 0): the cut lands on every centre row, after a
+    first point, inside a patch, after a last point, at the offered count and above it.  The bodies and the drop counters are the
+    oracle's; a list that holds the step gives the uncapped bits."""
+    se, batch = _cut_batch(sl, [(kind, 0)])
+    rows, steps = S.CUT_ROWS[kind], O.CUT_FRAMES * 4
+    prm = SB.default_params(frames=O.CUT_FRAMES)
+    full, caps = _cut_parity(se, oracle, batch, prm, "uncapped")
+    assert caps["max_contacts"] == rows and caps["contact_sum"] == steps * rows and caps["scenes_dropped"] == 0   # the cuts land where meant
+    for c in range(1, rows + 2):
+        prm["max_contacts_per_scene"] = c
+        gpu, caps = _cut_parity(se, oracle, batch, prm, "max_contacts_per_scene %d" % c)
+        if c >= rows:
+            assert caps["scenes_dropped"] == 0
+            assert_bodies_equal(gpu, full)
+        else:
+            assert caps["contact_drop_steps"] > 0
+
+
+def test_lone_centre_row_known_answer(sl, launch_form):
+    """max_contacts_per_scene = 1: the list holds the first slider's centre row alone -- a normal row along the table's normal, no
+    friction row -- so after 10 frames the slider's horizontal velocity is what it started with, bit for bit (no oracle)."""
+    se, (srec, bodies, hulls, verts) = _cut_batch(sl, [("sliders", 0)])
+    prm = SB.default_params(frames=10)
+    prm["max_contacts_per_scene"] = 1
+    gpu, caps = se.run_with_caps(srec, bodies.copy(), prm)
+    assert caps["contact_drop_steps"] == 40 and caps["contact_sum"] == 40
+    v = np.float32(S.CUT_VELOCITY)
+    assert gpu[0]["lin_vel"][0] == v[0] and gpu[0]["lin_vel"][1] == v[1], gpu[0]["lin_vel"]
+    assert np.isfinite(gpu["pose"]).all()
+
+
+def test_contact_capacity_cut_in_shared_solver_waves(sl, oracle, monkeypatch, launch_form):
+    """Six different scenes in one call, cut so that one or another keeps a lone centre row at the end of its list: in the lockstep
+    form with solver waves of one, two and four scenes (SLHIP_SOLVE_SPW), where the scenes' LDS shares lie back to back.  Every
+    scene is the oracle's, and the same call run again gives the same bits."""
+    kinds = [("sliders", 0), ("edge", 0), ("sliders", 1), ("edge", 1), ("sliders", 2), ("edge", 2)]
+    se, batch = _cut_batch(sl, kinds)
+    srec, bodies = batch[:2]
+    prm = SB.default_params(frames=O.CUT_FRAMES)
+    for c in (1, 3, 6, 8, 13, 16, 21):        # lone centres: sliders at 1, 6, 16, 21; edge at 3, 8, 13
+        prm["max_contacts_per_scene"] = c
+        for spw in (("1", "2", "4") if launch_form == "lockstep" else (None,)):
+            if spw is not None:
+                monkeypatch.setenv("SLHIP_SOLVE_SPW", spw)
+            gpu, caps = _cut_parity(se, oracle, batch, prm, "max_contacts_per_scene %d, SLHIP_SOLVE_SPW %s" % (c, spw))
+            assert caps["scenes_dropped"] == sum(S.CUT_ROWS[k] > c for k, _ in kinds)
+            again, _ = se.run_with_caps(srec, bodies.copy(), prm)
+            assert_bodies_equal(again, gpu)
+
+
+def test_contact_capacity_cut_beyond_the_lds_part(sl, oracle, monkeypatch, launch_form):
+    """The cut beyond the solver wave's LDS-resident part of the list, where solve_group sweeps the rows from global memory.  (i) 100
+    sliders (500 rows; a solver wave keeps ~300 of them in LDS in either form), cut on the last centre row, after it, inside the last
+    patch, at the offered count and above.  (ii) lockstep: one scene per solver wave (SLHIP_SOLVE_SPW 1) with the least LDS a wave
+    may have (SLHIP_SOLVE_LDS_KB 3: ~32 resident rows; a smaller value would be ignored -- spill_steps says it took), on a batch
+    whose last scene fits."""
+    se, batch = _cut_batch(sl, [("grid", 0)])
+    prm = SB.default_params(frames=2)
+    full, caps = _cut_parity(se, oracle, batch, prm, "grid, uncapped")
+    assert caps["max_contacts"] == S.CUT_ROWS["grid"] and caps["spill_steps"] > 0
+    for c in (496, 497, 499, 500, 501):
+        prm["max_contacts_per_scene"] = c
+        gpu, caps = _cut_parity(se, oracle, batch, prm, "grid, max_contacts_per_scene %d" % c)
+        assert caps["spill_steps"] > 0
+        if c >= S.CUT_ROWS["grid"]:
+            assert_bodies_equal(gpu, full)
+    if launch_form != "lockstep":
+        return
+    monkeypatch.setenv("SLHIP_SOLVE_SPW", "1")
+    monkeypatch.setenv("SLHIP_SOLVE_LDS_KB", "3")
+    se, batch = _cut_batch(sl, [("long", 0), ("long", 1), ("sliders", 0)])
+    prm = SB.default_params(frames=O.CUT_FRAMES)
+    for c in (36, 37, 39, 40, 41):              # 36: the last face patch keeps its centre row alone, beyond the resident part
+        prm["max_contacts_per_scene"] = c
+        _, caps = _cut_parity(se, oracle, batch, prm, "long, SLHIP_SOLVE_LDS_KB 3, max_contacts_per_scene %d" % c)
+        assert caps["spill_steps"] > 0 and caps["scenes_spilled"] == 2
+
+
+@pytest.mark.parametrize("cap", [16, 21])
+def test_resume_across_a_lone_centre_cut(sl, oracle, cap):
+    """A capacity that leaves a lone centre row: at 16 the column's table patch (the carried impulse behind PlanePM's flag word), at
+    21 the column's face patch (PM.pad[0], its c_off at the list's capacity).  Five one-frame calls on the same scratch == one
+    five-frame call == the oracle."""
+    se, batch = _cut_batch(sl, [("sliders", 0), ("sliders", 1)])
+    srec, bodies, hulls, verts = batch
+    frames = 5
+    prm = SB.default_params(frames=frames)
+    prm["max_contacts_per_scene"] = cap
+    one, caps = _cut_parity(se, oracle, batch, prm, "max_contacts_per_scene %d" % cap)
+    assert caps["contact_drop_steps"] > 0
+    d_b = se.eng.upload_records(bodies.copy())
+    for f in range(frames):
+        p1 = SB.default_params(frames=1)
+        p1["max_contacts_per_scene"] = cap
+        p1["resume"] = 4 * f
+        d_b = se.run_device(srec, None, SB.sizing_hints(p1, srec, bodies, hulls), d_bodies=d_b)
+    many = np.frombuffer(d_b.cpu().numpy().tobytes(), dtype=SB.BODY_DTYPE).copy()
+    assert_bodies_equal(many, one)
+
+
+def test_pair_capacities_around_the_offered_count(sl, oracle):
+    """max_hull_pairs_per_scene and max_body_pairs_per_scene at the offered count - 1, the offered count and + 1 (three cubes side
+    by side on the table: two hull pairs, and two body pairs beside a table group per body -- the group list holds one group per
+    body and max_body_pairs_per_scene more): what does not fit is dropped and counted identically on both sides, and a list that
+    holds the step drops nothing and gives the uncapped bits."""
+    se, batch = _cut_batch(sl, [("row", 0), ("row", 1)])
+    prm0 = SB.default_params(frames=O.CUT_FRAMES)
+    full, caps = _cut_parity(se, oracle, batch, prm0, "uncapped")
+    offered = S.CUT_PAIRS["row"]
+    assert caps["max_hull_pairs"] == offered and caps["scenes_dropped"] == 0
+    for key, word in (("max_hull_pairs_per_scene", "pair_drop_steps"), ("max_body_pairs_per_scene", "group_drop_steps")):
+        for cap in (offered - 1, offered, offered + 1):
+            prm = prm0.copy()
+            prm[key] = cap
+            gpu, caps = _cut_parity(se, oracle, batch, prm, "%s %d" % (key, cap))
+            if cap >= offered:
+                assert caps["scenes_dropped"] == 0
+                assert_bodies_equal(gpu, full)
+            else:
+                assert caps[word] > 0 and caps["scenes_dropped"] == 2

@@ -280,3 +280,92 @@ def test_contact_state_outlives_the_call(sl, oracle):
     prm["resume"] = 7
     with pytest.raises(RuntimeError):
         oracle.settle(srec, many, hulls, verts, prm, state=st)
+
+
+# ---- the per-scene contact list's capacity: the cut rule the GPU parity tests compare against -----------------------------------
+CUT_FRAMES = 3            # 12 steps: the sliders are still sliding at the end
+
+
+def cut_batch(sl, kinds):
+    """A batch of S.cut_scene scenes on a table: (srec, bodies, hulls, verts); `kinds` = [(kind, variant), ...]."""
+    pool = SB.HullPool()
+    scs = [S.cut_scene(sl, k, v) for k, v in kinds]
+    srec, bodies = SB.build_settle_batch(scs, pool, [(True, S.CUT_TABLE)] * len(scs))
+    hulls, verts = pool.arrays()
+    return srec, bodies, hulls, verts
+
+
+def settle_with_caps(oracle, batch, prm, state=None):
+    """The oracle on a copy of the batch's bodies with its per-scene counters (slref_settle_set_caps): (bodies, uint32[S, 7] =
+    steps that dropped contacts, steps that dropped hull pairs, most contacts offered, most hull pairs found, reduced steps, steps
+    that dropped body pairs, contacts the solver took)."""
+    import ctypes as C
+
+    srec, bodies, hulls, verts = batch
+    L = oracle.lib()
+    oc = np.zeros((len(srec), 7), np.uint32)
+    L.slref_settle_set_caps.argtypes = [C.c_void_p]
+    L.slref_settle_set_caps(C.c_void_p(oc.ctypes.data))
+    out = bodies.copy()
+    try:
+        oracle.settle(srec, out, hulls, verts, SB.sizing_hints(prm, srec, bodies, hulls), state=state)
+    finally:
+        L.slref_settle_set_caps(None)
+    return out, oc
+
+
+@pytest.mark.parametrize("kind", ["sliders", "edge", "long"])
+def test_contact_capacity_cut_at_every_row(sl, oracle, kind):
+    """max_contacts_per_scene = C below what a step offers: the step keeps the first C rows in list order -- a patch's centre row,
+    then its points -- and is counted.  Swept over every cut: on each centre row (the patch keeps its centre alone), after a first
+    point, inside a patch, after a last point, at the offered count and above it.  Up to the last patch's centre row every step
+    overflows; a cut among the points of the last patch (a hull pair's) leaves fewer points in its manifold, so the next step may
+    offer no more than C."""
+    batch = cut_batch(sl, [(kind, 0)])
+    rows, steps = S.CUT_ROWS[kind], CUT_FRAMES * 4
+    prm = SB.default_params(frames=CUT_FRAMES)
+    full, oc = settle_with_caps(oracle, batch, prm)
+    assert oc[0].tolist() == [0, 0, rows, S.CUT_PAIRS[kind], 0, 0, steps * rows]     # the row structure the cuts rely on
+    for c in range(1, rows + 2):
+        prm["max_contacts_per_scene"] = c
+        out, oc = settle_with_caps(oracle, batch, prm)
+        drops, offered, taken = int(oc[0, 0]), int(oc[0, 2]), int(oc[0, 6])
+        assert np.isfinite(out["pose"]).all() and np.isfinite(out["lin_vel"]).all() and np.isfinite(out["ang_vel"]).all(), c
+        assert offered == rows and oc[0, 1] == 0 and oc[0, 5] == 0, (c, oc[0])
+        if c >= rows:
+            assert drops == 0 and taken == steps * rows, (c, oc[0])
+            assert out.tobytes() == full.tobytes(), c                                  # a list that holds the step: the uncapped bits
+        elif c <= rows - 4:
+            assert drops == steps and taken == steps * c, (c, oc[0])
+        else:
+            assert 0 < drops < steps and drops * c <= taken <= steps * c, (c, oc[0])
+            assert out.tobytes() != full.tobytes(), c
+
+
+def test_contact_capacity_cut_on_a_grid(sl, oracle):
+    """100 sliders (table patches only, 500 rows): every step overflows at every cut below the offered count, the last centre
+    row alone (496) included."""
+    batch = cut_batch(sl, [("grid", 0)])
+    rows, steps = S.CUT_ROWS["grid"], 2 * 4
+    prm = SB.default_params(frames=2)
+    full, oc = settle_with_caps(oracle, batch, prm)
+    assert oc[0].tolist() == [0, 0, rows, 0, 0, 0, steps * rows]
+    for c in (1, 3, 251, 496, 497, 499, 500, 501):
+        prm["max_contacts_per_scene"] = c
+        out, oc = settle_with_caps(oracle, batch, prm)
+        assert np.isfinite(out["pose"]).all() and np.isfinite(out["lin_vel"]).all(), c
+        assert oc[0, 0] == (steps if c < rows else 0) and oc[0, 6] == steps * min(c, rows), (c, oc[0])
+        assert (out.tobytes() == full.tobytes()) == (c >= rows), c
+
+
+def test_lone_centre_row_known_answer(sl, oracle):
+    """max_contacts_per_scene = 1: the list holds the first slider's centre row and nothing else.  That row acts along the table's
+    normal only and no friction row runs, so over 10 frames the slider's horizontal velocity comes back bit for bit."""
+    batch = cut_batch(sl, [("sliders", 0)])
+    prm = SB.default_params(frames=10)
+    prm["max_contacts_per_scene"] = 1
+    out, oc = settle_with_caps(oracle, batch, prm)
+    assert oc[0, 0] == 40 and oc[0, 6] == 40
+    v = np.float32(S.CUT_VELOCITY)
+    assert out[0]["lin_vel"][0] == v[0] and out[0]["lin_vel"][1] == v[1]
+    assert np.isfinite(out["pose"]).all()

@@ -634,6 +634,10 @@ int slhip_stream_destroy(void* stream);
  * 0x51DE5EED); uniform = ((x >> 8) + 0.5) * 2^-24; normals by Box-Muller on deterministic log /
  * sin / cos polynomials (the DISTRIBUTIONS of the reference are the contract, its libstdc++ streams are
  * not reproducible: it seeds from std::random_device, scene.cpp:147-148).
+ * Streams: 0 scene (plane yaw, camera azimuth / elevation, light direction), 1 classes, 2 orientations, 3 metallic /
+ * roughness, 4 environment (slhip_synth_place_env only; no draw of streams 0-3 depends on it).  Stream 4, index 0:
+ * x[0] gates the light set, x[1] picks it, x[2] gates the background image, x[3] picks it; index 1: x[0] gates the plane
+ * texture, x[1] picks it.  Gate: uniform(x) < p.  Pick: min(n - 1, (uint32_t)(uniform(x) * (float)n)), float32 throughout.
  * ------------------------------------------------------------------------------------------- */
 
 /* One mesh class: what sl.Mesh (+ the defaults of sl.Object) contributes to a scene. */
@@ -658,7 +662,7 @@ typedef struct {
                                            d_asset_ids names every object's class                     */
 #define SLHIP_SYNTH_RANDOM_PBR      2u  /* metallic, roughness ~ U(0,1) per object (examples/ycb.py:63-64:
                                            obj.metallic / obj.roughness); otherwise the file's values   */
-#define SLHIP_SYNTH_SHADOWS         4u  /* fill shadow_mat of the active light (render_pass.cpp:131-211) */
+#define SLHIP_SYNTH_SHADOWS         4u  /* fill shadow_mat of the active light(s) (render_pass.cpp:131-211) */
 #define SLHIP_SYNTH_MAX_ASSETS   1024u
 #define SLHIP_SYNTH_MAX_OBJECTS    64u  /* == SLHIP_MAX_BODIES */
 
@@ -707,6 +711,48 @@ int slhip_synth_stage(const slhip_synth_params* params, const slhip_asset* d_ass
 int slhip_synth_place(const slhip_synth_params* params, const slhip_asset* d_assets, const slhip_draw* d_templates,
                       const slhip_body* d_bodies, const slhip_synth_object* d_objects, slhip_synth_scene* d_scenes,
                       slhip_scene* d_out_scenes, slhip_draw* d_out_draws, slhip_chunk* d_out_chunks, void* stream);
+
+/* The environment bank of a batch: what examples/ycb.py binds per scene with --ibl (:64-67, Scene::setLightMap) and
+ * --plane-texture (:73-74, Scene::setBackgroundPlaneTexture), and Scene::setBackgroundImage (py_scene.cpp:131-140),
+ * uploaded once like the asset table.  The textures live in the texel pool handed to slhip_render (d_tex).        */
+typedef struct {            /* one light map as a scene uses it (render_pass.cpp:412-418, render_shader.cpp:270-296) */
+    uint32_t light_map;     /* 1 + index into slhip_mesh_pool.d_light_maps                                   */
+    uint32_t n_lights;      /* <= SLHIP_NUM_LIGHTS (more are cut, render_pass.cpp:417-418): Sun / Light1 / Light2 of
+                               the .ibl file (light_map.cpp:310-345)                                          */
+    uint32_t _pad[2];
+    float light_dir[SLHIP_NUM_LIGHTS][4], light_color[SLHIP_NUM_LIGHTS][4];   /* world frame (xyz)            */
+} slhip_env_light_set;      /* 112 bytes */
+
+typedef struct {            /* a texture of the texel pool: Scene::backgroundImage (render_pass.cpp:637-646) or   */
+    uint32_t offset, w, h;  /* Scene::backgroundPlaneTexture (render_pass.cpp:555-573); byte offset, size          */
+    uint32_t sampler;       /* SLHIP_SAMPLER_* of the plane draw's base texture (low 8 bits); unused for backgrounds */
+} slhip_env_texture;        /* 16 bytes */
+
+typedef struct {
+    const slhip_env_light_set* d_light_sets;     /* Scene::lightMap candidates (scene.h:174-176)                */
+    const slhip_env_texture*   d_backgrounds;    /* rectangle textures, one level (py_scene.cpp:131-140)       */
+    const slhip_env_texture*   d_plane_textures; /* 2D textures with mip chain (py_scene.cpp:414-415)          */
+    const int32_t* d_env_ids;   /* NULL: draw from stream 4.  Else [n_scenes][3] = (light set, background, plane
+                                   texture) of every scene, -1 = none; an id beyond its bank makes the scene EMPTY
+                                   (no draws -- as for record strides that do not fit), nothing is read out of bounds */
+    uint32_t n_light_sets, n_backgrounds, n_plane_textures;
+    float p_light_map, p_background, p_plane_texture;   /* probability that a scene gets one, each in [0, 1]
+                                   (examples/ycb.py:64-74 takes all or none per run); ignored with d_env_ids     */
+} slhip_synth_env;          /* 56 bytes */
+
+/* slhip_synth_place with an environment per scene.  Camera, draws of the objects and chunks are those of
+ * slhip_synth_place bit for bit.  A scene WITHOUT a light set gets the drawn light, params->light_color and
+ * params->ambient as there; WITH one, light l < n_lights = the set's direction / colour, the others off, ambient 0,
+ * light_map = the set's (render_pass.cpp:412-418; RenderShader::setLightMap, render_shader.cpp:270-296).  With
+ * SLHIP_SYNTH_SHADOWS every active light gets its shadow matrix (render_pass.cpp:131-211, 426-436), by the arithmetic
+ * light 0 has in slhip_synth_place.  bg_tex and the plane draw's base texture (colour 1, SLHIP_DRAW_HAS_BASE_TEX;
+ * render_pass.cpp:555-573) come from the bank entries.  d_env_out [n_scenes][3]: what each scene got, -1 = none.
+ * Refused before any launch: a null bank with a non-zero count, a probability outside [0, 1] or not finite, a
+ * probability above zero for an empty bank (when drawing), a null d_env_out.                                    */
+int slhip_synth_place_env(const slhip_synth_params* params, const slhip_synth_env* env, const slhip_asset* d_assets,
+                          const slhip_draw* d_templates, const slhip_body* d_bodies, const slhip_synth_object* d_objects,
+                          slhip_synth_scene* d_scenes, slhip_scene* d_out_scenes, slhip_draw* d_out_draws,
+                          slhip_chunk* d_out_chunks, int32_t* d_env_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Host side of the per-object API (sl.Scene / sl.RenderPass): record assembly in C++, one call per batch.

@@ -9,6 +9,7 @@ from stillleben_amd import camera_model, diff, extension, losses, profiling  # n
 from .lib.libstillleben_python import *  # noqa: F401,F403
 from .lib.libstillleben_python import _set_install_prefix  # noqa: F401
 from stillleben_amd import AssetTable, SceneBatch  # noqa: F401  (additive: the batch dimension of the GPU path)
+from stillleben_amd import EnvironmentBank  # noqa: F401  (additive: the environment bank of a SceneBatch)
 from stillleben_amd import ObjectStats  # noqa: F401  (additive: per-object visibility statistics)
 
 __all__ = _impl.__all__

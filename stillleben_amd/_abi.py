@@ -222,6 +222,31 @@ assert SYNTH_PARAMS_DTYPE.itemsize == 224
 SYNTH_OBJECT_DTYPE = np.dtype([("asset", np.uint32), ("instance_index", np.uint32), ("metallic", np.float32),
                                ("roughness", np.float32)])
 SYNTH_SCENE_DTYPE = np.dtype([("plane_pose", np.float32, (16,)), ("camera_pose", np.float32, (16,))])
+# slhip_env_light_set / slhip_env_texture / slhip_synth_env (include/slhip.h): the environment bank of slhip_synth_place_env
+ENV_LIGHT_SET_DTYPE = np.dtype([("light_map", np.uint32), ("n_lights", np.uint32), ("_pad", np.uint32, (2,)),
+                                ("light_dir", np.float32, (NUM_LIGHTS, 4)), ("light_color", np.float32, (NUM_LIGHTS, 4))])
+assert ENV_LIGHT_SET_DTYPE.itemsize == 112
+ENV_TEXTURE_DTYPE = np.dtype([("offset", np.uint32), ("w", np.uint32), ("h", np.uint32), ("sampler", np.uint32)])
+assert ENV_TEXTURE_DTYPE.itemsize == 16
+
+
+class SynthEnv(C.Structure):
+    _fields_ = [
+        ("d_light_sets", C.c_void_p),
+        ("d_backgrounds", C.c_void_p),
+        ("d_plane_textures", C.c_void_p),
+        ("d_env_ids", C.c_void_p),
+        ("n_light_sets", C.c_uint32),
+        ("n_backgrounds", C.c_uint32),
+        ("n_plane_textures", C.c_uint32),
+        ("p_light_map", C.c_float),
+        ("p_background", C.c_float),
+        ("p_plane_texture", C.c_float),
+    ]
+
+
+assert C.sizeof(SynthEnv) == 56
+SYNTH_STREAM_ENV = 4      # Philox stream of the environment draws (include/slhip.h, "Randomness")
 SYNTH_SAMPLE_DISTINCT = 1
 SYNTH_RANDOM_PBR = 2
 SYNTH_SHADOWS = 4
@@ -302,6 +327,8 @@ def lib():
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8
     L.slhip_synth_place.argtypes = [C.c_void_p] * 10
+    if hasattr(L, "slhip_synth_place_env"):          # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_synth_place_env.argtypes = [C.c_void_p, C.POINTER(SynthEnv)] + [C.c_void_p] * 10
     L.slhip_comm_unique_id.argtypes = [C.c_void_p]
     L.slhip_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.slhip_comm_destroy.argtypes = [C.c_void_p]

@@ -38,7 +38,7 @@ __device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, ui
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-enum { STREAM_SCENE = 0, STREAM_ASSETS = 1, STREAM_QUAT = 2, STREAM_PBR = 3 };
+enum { STREAM_SCENE = 0, STREAM_ASSETS = 1, STREAM_QUAT = 2, STREAM_PBR = 3, STREAM_ENV = 4 };
 
 __device__ __forceinline__ void draw4(const slhip_synth_params& p, uint32_t scene, uint32_t stream, uint32_t idx,
                                       uint32_t out[4])
@@ -344,12 +344,115 @@ __global__ __launch_bounds__(64) void k_synth_stage(slhip_synth_params p, const 
 }
 
 // ------------------------------------------------------------------------------------------ place
+// Depth range of the camera frustum over the objects (computeFrustumCorners, render_pass.cpp:69-129): the part of the
+// shadow fit that no light enters.  Wave-uniform call; every lane returns the reduced values.
+__device__ __forceinline__ void frustum_depth_range(const slhip_synth_params& p, const float* w2c, const float* pose,
+                                                    const float* bc, float radius, bool has_obj, float& near, float& far)
+{
+    const float INF = __uint_as_float(0x7F800000u);
+    float near_obj = INF, far_obj = -INF;
+    if (has_obj) {
+        float M[16], cc[3];
+        mm4(w2c, pose, M);
+        xform_point(M, bc, cc);
+        const float np[4] = {cc[0], cc[1], cc[2] - radius, 1.0f}, fp[4] = {cc[0], cc[1], cc[2] + radius, 1.0f};
+        float qn[4], qf[4];
+        mv4(p.proj, np, qn);
+        mv4(p.proj, fp, qf);
+        near_obj = qn[2] / qn[3];
+        far_obj = qf[2] / qf[3];
+    }
+    near_obj = wave_min(near_obj);
+    far_obj = wave_max(far_obj);
+    near = fmaxf(fmaxf(-1.0f, near_obj), -1.0f);
+    far = fminf(far_obj, 1.0f);
+}
+
+// World -> light clip matrix of one directional light (computeShadowMapMatrix, render_pass.cpp:131-211): light frame, bounds of
+// the 8 frustum corners, clamp to the objects' spheres.  Wave-uniform call; identity when the fit is not finite.
+__device__ __forceinline__ void fit_shadow_matrix(const slhip_synth_params& p, const float* ld, float near, float far,
+                                                  const float* c2w, const float* pose, const float* bc, float radius,
+                                                  bool has_obj, float* sm)
+{
+    const float INF = __uint_as_float(0x7F800000u);
+    float z[3] = {ld[0], ld[1], ld[2]}, xa[3], ya[3];
+    normalize3(z);
+    const float up[3] = {0.0f, 0.0f, 1.0f};
+    cross3(z, up, xa);
+    normalize3(xa);
+    cross3(z, xa, ya);
+    normalize3(ya);
+    float l2w[16], w2l[16];
+    identity4(l2w);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { l2w[4 * r + 0] = xa[r]; l2w[4 * r + 1] = ya[r]; l2w[4 * r + 2] = z[r]; }
+    inv_rigid(l2w, w2l);
+    float mnv[3] = {INF, INF, INF}, mxv[3] = {-INF, -INF, -INF};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const float sx = (i == 1 || i == 2 || i == 5 || i == 6) ? 1.0f : -1.0f;
+        const float sy = ((i & 3) < 2) ? 1.0f : -1.0f;
+        const float h[4] = {sx, sy, i < 4 ? near : far, 1.0f};
+        float t0[4], t1[4], corner[3], qv[3];
+        mv4(p.proj_inv, h, t0);
+        mv4(c2w, t0, t1);
+        corner[0] = t1[0] / t1[3]; corner[1] = t1[1] / t1[3]; corner[2] = t1[2] / t1[3];
+        xform_point(w2l, corner, qv);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { mnv[k] = fminf(mnv[k], qv[k]); mxv[k] = fmaxf(mxv[k], qv[k]); }
+    }
+    float near_l = mnv[2], far_l = mxv[2];
+    const float mean_z = (near_l + far_l) / 2.0f;
+    const float spread = far_l - mean_z;
+    far_l = mean_z + 5.0f * spread;
+    near_l = mean_z - 5.0f * spread;
+    float L = mnv[0], R = mxv[0], T = mnv[1], B = mxv[1];
+    float lo[2] = {INF, INF}, hi[2] = {-INF, -INF};
+    if (has_obj) {
+        float M[16], cc[3];
+        mm4(w2l, pose, M);
+        xform_point(M, bc, cc);
+        lo[0] = cc[0] - radius; lo[1] = cc[1] - radius;
+        hi[0] = cc[0] + radius; hi[1] = cc[1] + radius;
+    }
+    L = fmaxf(L, wave_min(lo[0])); R = fminf(R, wave_max(hi[0]));
+    T = fmaxf(T, wave_min(lo[1])); B = fminf(B, wave_max(hi[1]));
+    float Pm[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) Pm[i] = 0.0f;
+    Pm[0] = 2.0f / (R - L); Pm[3] = -(R + L) / (R - L);
+    Pm[5] = 2.0f / (B - T); Pm[7] = -(B + T) / (B - T);
+    Pm[10] = 2.0f / (far_l - near_l); Pm[11] = -(far_l + near_l) / (far_l - near_l);
+    Pm[15] = 1.0f;
+    mm4(Pm, w2l, sm);
+    if (!finite16(sm)) identity4(sm);
+}
+
+__device__ __forceinline__ bool light_active(const float* dir, const float* color)
+{
+    return (color[0] != 0.0f || color[1] != 0.0f || color[2] != 0.0f) && (dir[0] != 0.0f || dir[1] != 0.0f || dir[2] != 0.0f);
+}
+
+// What the environment form of k_synth_place gets on top of the plain arguments; the plain form carries nothing.
+struct env_args {
+    slhip_synth_env env;
+    int32_t* env_out;
+};
+struct no_env_args {};
+template <bool kEnv> struct place_env { typedef no_env_args type; };
+template <> struct place_env<true> { typedef env_args type; };
+
+// kEnv = false: the record slhip_synth_place has always written (one drawn light, green plane, cleared background).
+// kEnv = true: every scene additionally takes a light set / background image / plane texture of the environment bank, drawn
+// from STREAM_ENV or named by d_env_ids, and every active light gets its shadow matrix.
+template <bool kEnv>
 __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const slhip_asset* __restrict__ assets,
                                                    const slhip_draw* __restrict__ templates,
                                                    const slhip_body* __restrict__ bodies_all,
                                                    const slhip_synth_object* __restrict__ objects_all,
                                                    slhip_synth_scene* __restrict__ scenes, slhip_scene* __restrict__ out_scenes,
-                                                   slhip_draw* __restrict__ out_draws, slhip_chunk* __restrict__ out_chunks)
+                                                   slhip_draw* __restrict__ out_draws, slhip_chunk* __restrict__ out_chunks,
+                                                   typename place_env<kEnv>::type ea)
 {
     __shared__ slhip_scene sc_s;
     __shared__ uint32_t obj_nd[SLHIP_SYNTH_MAX_OBJECTS + 1], obj_nk[SLHIP_SYNTH_MAX_OBJECTS + 1];
@@ -453,83 +556,95 @@ __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const 
             ld[r] = t;
         }
     }
-    const bool light_on = (p.light_color[0] != 0.0f || p.light_color[1] != 0.0f || p.light_color[2] != 0.0f) &&
-                          (ld[0] != 0.0f || ld[1] != 0.0f || ld[2] != 0.0f);
+    // ---- environment of the scene (kEnv): light set, background image, plane texture ----
+    int32_t env_id[3] = {-1, -1, -1};      // wave-uniform
+    bool env_ok = true;
+    if constexpr (kEnv) {
+        const slhip_synth_env& e = ea.env;
+        const uint32_t n_bank[3] = {e.n_light_sets, e.n_backgrounds, e.n_plane_textures};
+        if (e.d_env_ids) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                env_id[k] = e.d_env_ids[(size_t)s * 3 + k];
+                // an id beyond its bank: the scene is written EMPTY (below), nothing of the bank is read
+                if (env_id[k] < -1 || (env_id[k] >= 0 && (uint32_t)env_id[k] >= n_bank[k])) env_ok = false;
+            }
+        } else {
+            uint32_t y[4];
+            draw4(p, s, STREAM_ENV, 0, x);
+            draw4(p, s, STREAM_ENV, 1, y);
+            const uint32_t gate[3] = {x[0], x[2], y[0]}, pick[3] = {x[1], x[3], y[1]};
+            const float prob[3] = {e.p_light_map, e.p_background, e.p_plane_texture};
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (n_bank[k] > 0 && u01(gate[k]) < prob[k]) {
+                    const uint32_t j = (uint32_t)(u01(pick[k]) * (float)n_bank[k]);
+                    env_id[k] = (int32_t)(j < n_bank[k] - 1 ? j : n_bank[k] - 1);
+                }
+        }
+        if (!env_ok) { env_id[0] = -1; env_id[1] = -1; env_id[2] = -1; }
+    }
 
-    // ---- shadow matrix of light 0 (render_pass.cpp:69-211) ----
     float sm[16];
-    identity4(sm);
-    if ((p.flags & SLHIP_SYNTH_SHADOWS) && light_on) {
+    if constexpr (!kEnv) {
+        // ---- shadow matrix of light 0 (render_pass.cpp:69-211) ----
+        const bool light_on = light_active(ld, p.light_color);
+        identity4(sm);
+        if ((p.flags & SLHIP_SYNTH_SHADOWS) && light_on) {
+            float bc[3];
+            bbox_center(a, bc);
+            const float radius = bbox_diagonal(a) / 2.0f;
+            float near, far;
+            frustum_depth_range(p, w2c, pose, bc, radius, has_obj, near, far);
+            fit_shadow_matrix(p, ld, near, far, c2w, pose, bc, radius, has_obj, sm);
+        }
+    } else {
+        // ---- lights, ambient, light map, background of the scene record, assembled in LDS: lane l owns light l ----
+        for (uint32_t i = lane; i < sizeof(slhip_scene) / 4; i += 64) reinterpret_cast<uint32_t*>(&sc_s)[i] = 0u;
+        __syncthreads();
+        if (lane < SLHIP_NUM_LIGHTS) {
+            float d[3] = {0.0f, 0.0f, 0.0f}, c[3] = {0.0f, 0.0f, 0.0f};
+            if (env_id[0] >= 0) {
+                // render_pass.cpp:412-418, render_shader.cpp:270-296: the map's lights replace the scene's, no ambient term
+                const slhip_env_light_set& ls = ea.env.d_light_sets[env_id[0]];
+                const uint32_t n = ls.n_lights < SLHIP_NUM_LIGHTS ? ls.n_lights : SLHIP_NUM_LIGHTS;
+                if (lane < n) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) { d[k] = ls.light_dir[lane][k]; c[k] = ls.light_color[lane][k]; }
+                }
+                if (lane == 0) sc_s.light_map = ls.light_map;
+            } else if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { d[k] = ld[k]; c[k] = p.light_color[k]; sc_s.ambient[k] = p.ambient[k]; }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { sc_s.light_dir[lane][k] = d[k]; sc_s.light_color[lane][k] = c[k]; }
+            if (lane == 0 && env_id[1] >= 0) {
+                const slhip_env_texture t = ea.env.d_backgrounds[env_id[1]];
+                sc_s.bg_tex[0] = t.offset; sc_s.bg_tex[1] = t.w; sc_s.bg_tex[2] = t.h;
+            }
+        }
+        __syncthreads();
+        // ---- shadow matrix of every active light (render_pass.cpp:69-211); the frustum part once ----
         float bc[3];
         bbox_center(a, bc);
         const float radius = bbox_diagonal(a) / 2.0f;
-        float near_obj = INF, far_obj = -INF;
-        if (has_obj) {
-            float M[16], cc[3];
-            mm4(w2c, pose, M);
-            xform_point(M, bc, cc);
-            const float np[4] = {cc[0], cc[1], cc[2] - radius, 1.0f}, fp[4] = {cc[0], cc[1], cc[2] + radius, 1.0f};
-            float qn[4], qf[4];
-            mv4(p.proj, np, qn);
-            mv4(p.proj, fp, qf);
-            near_obj = qn[2] / qn[3];
-            far_obj = qf[2] / qf[3];
+        float near = 0.0f, far = 0.0f;
+        if (p.flags & SLHIP_SYNTH_SHADOWS) frustum_depth_range(p, w2c, pose, bc, radius, has_obj, near, far);
+#pragma unroll 1
+        for (int l = 0; l < SLHIP_NUM_LIGHTS; ++l) {
+            const float dl[3] = {sc_s.light_dir[l][0], sc_s.light_dir[l][1], sc_s.light_dir[l][2]};
+            const float cl[3] = {sc_s.light_color[l][0], sc_s.light_color[l][1], sc_s.light_color[l][2]};
+            identity4(sm);
+            if ((p.flags & SLHIP_SYNTH_SHADOWS) && light_active(dl, cl))
+                fit_shadow_matrix(p, dl, near, far, c2w, pose, bc, radius, has_obj, sm);
+            if (lane < 16) {
+                float v = sm[0];
+#pragma unroll
+                for (int i = 1; i < 16; ++i) v = lane == i ? sm[i] : v;
+                sc_s.shadow_mat[l][lane] = v;
+            }
         }
-        near_obj = wave_min(near_obj);
-        far_obj = wave_max(far_obj);
-        const float near = fmaxf(fmaxf(-1.0f, near_obj), -1.0f);
-        const float far = fminf(far_obj, 1.0f);
-        float z[3] = {ld[0], ld[1], ld[2]}, xa[3], ya[3];
-        normalize3(z);
-        const float up[3] = {0.0f, 0.0f, 1.0f};
-        cross3(z, up, xa);
-        normalize3(xa);
-        cross3(z, xa, ya);
-        normalize3(ya);
-        float l2w[16], w2l[16];
-        identity4(l2w);
-#pragma unroll
-        for (int r = 0; r < 3; ++r) { l2w[4 * r + 0] = xa[r]; l2w[4 * r + 1] = ya[r]; l2w[4 * r + 2] = z[r]; }
-        inv_rigid(l2w, w2l);
-        float mnv[3] = {INF, INF, INF}, mxv[3] = {-INF, -INF, -INF};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float sx = (i == 1 || i == 2 || i == 5 || i == 6) ? 1.0f : -1.0f;
-            const float sy = ((i & 3) < 2) ? 1.0f : -1.0f;
-            const float h[4] = {sx, sy, i < 4 ? near : far, 1.0f};
-            float t0[4], t1[4], corner[3], qv[3];
-            mv4(p.proj_inv, h, t0);
-            mv4(c2w, t0, t1);
-            corner[0] = t1[0] / t1[3]; corner[1] = t1[1] / t1[3]; corner[2] = t1[2] / t1[3];
-            xform_point(w2l, corner, qv);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { mnv[k] = fminf(mnv[k], qv[k]); mxv[k] = fmaxf(mxv[k], qv[k]); }
-        }
-        float near_l = mnv[2], far_l = mxv[2];
-        const float mean_z = (near_l + far_l) / 2.0f;
-        const float spread = far_l - mean_z;
-        far_l = mean_z + 5.0f * spread;
-        near_l = mean_z - 5.0f * spread;
-        float L = mnv[0], R = mxv[0], T = mnv[1], B = mxv[1];
-        float lo[2] = {INF, INF}, hi[2] = {-INF, -INF};
-        if (has_obj) {
-            float M[16], cc[3];
-            mm4(w2l, pose, M);
-            xform_point(M, bc, cc);
-            lo[0] = cc[0] - radius; lo[1] = cc[1] - radius;
-            hi[0] = cc[0] + radius; hi[1] = cc[1] + radius;
-        }
-        L = fmaxf(L, wave_min(lo[0])); R = fminf(R, wave_max(hi[0]));
-        T = fmaxf(T, wave_min(lo[1])); B = fminf(B, wave_max(hi[1]));
-        float Pm[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) Pm[i] = 0.0f;
-        Pm[0] = 2.0f / (R - L); Pm[3] = -(R + L) / (R - L);
-        Pm[5] = 2.0f / (B - T); Pm[7] = -(B + T) / (B - T);
-        Pm[10] = 2.0f / (far_l - near_l); Pm[11] = -(far_l + near_l) / (far_l - near_l);
-        Pm[15] = 1.0f;
-        mm4(Pm, w2l, sm);
-        if (!finite16(sm)) identity4(sm);
     }
 
     // ---- per-object record counts, prefix over the scene's objects ----
@@ -553,33 +668,47 @@ __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const 
     const uint32_t d0 = local * p.max_draws_per_scene;
     // strides too small for this scene (a host error: the strides come from the asset table's maxima): write the
     // scene EMPTY rather than out of bounds -- an all-background image is impossible to miss
-    const bool fits = nd_total <= p.max_draws_per_scene && nk_total <= p.max_chunks_per_scene;
+    const bool fits = nd_total <= p.max_draws_per_scene && nk_total <= p.max_chunks_per_scene && env_ok;
     if (!fits) { nd_total = 0; nk_total = 0; prim_total = 0; }
     slhip_draw* draws = out_draws + (size_t)s * p.max_draws_per_scene;
     slhip_chunk* chunks = out_chunks + (size_t)s * p.max_chunks_per_scene;
     const uint32_t clip_base_scene = local * p.max_clip_verts_per_scene;
 
     // ---- scene record (lane 0 assembles it in LDS, the wave stores it) ----
-    if (lane == 0) {
-        slhip_scene sc;
-        memset(&sc, 0, sizeof(sc));
+    if constexpr (!kEnv) {
+        if (lane == 0) {
+            slhip_scene sc;
+            memset(&sc, 0, sizeof(sc));
 #pragma unroll
-        for (int i = 0; i < 16; ++i) { sc.proj[i] = p.proj[i]; sc.world_to_cam[i] = w2c[i]; }
-        sc.cam_position[0] = c2w[3]; sc.cam_position[1] = c2w[7]; sc.cam_position[2] = c2w[11]; sc.cam_position[3] = 1.0f;
-        sc.light_dir[0][0] = ld[0]; sc.light_dir[0][1] = ld[1]; sc.light_dir[0][2] = ld[2];
+            for (int i = 0; i < 16; ++i) { sc.proj[i] = p.proj[i]; sc.world_to_cam[i] = w2c[i]; }
+            sc.cam_position[0] = c2w[3]; sc.cam_position[1] = c2w[7]; sc.cam_position[2] = c2w[11]; sc.cam_position[3] = 1.0f;
+            sc.light_dir[0][0] = ld[0]; sc.light_dir[0][1] = ld[1]; sc.light_dir[0][2] = ld[2];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { sc.light_color[0][i] = p.light_color[i]; sc.ambient[i] = p.ambient[i]; }
+            for (int i = 0; i < 3; ++i) { sc.light_color[0][i] = p.light_color[i]; sc.ambient[i] = p.ambient[i]; }
 #pragma unroll
-        for (int l = 0; l < SLHIP_NUM_LIGHTS; ++l)
+            for (int l = 0; l < SLHIP_NUM_LIGHTS; ++l)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) sc.shadow_mat[l][i] = l == 0 ? sm[i] : ((i % 5 == 0) ? 1.0f : 0.0f);
-        sc.manual_exposure = p.manual_exposure;
-        sc.draw_begin = d0;
-        sc.draw_end = d0 + nd_total;
-        sc.n_prims = prim_total;
-        sc_s = sc;
+                for (int i = 0; i < 16; ++i) sc.shadow_mat[l][i] = l == 0 ? sm[i] : ((i % 5 == 0) ? 1.0f : 0.0f);
+            sc.manual_exposure = p.manual_exposure;
+            sc.draw_begin = d0;
+            sc.draw_end = d0 + nd_total;
+            sc.n_prims = prim_total;
+            sc_s = sc;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) scenes[s].camera_pose[i] = cam[i];
+        }
+    } else if (lane == 0) {       // lights, shadow matrices, light map and background are in place
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { sc_s.proj[i] = p.proj[i]; sc_s.world_to_cam[i] = w2c[i]; }
+        sc_s.cam_position[0] = c2w[3]; sc_s.cam_position[1] = c2w[7]; sc_s.cam_position[2] = c2w[11]; sc_s.cam_position[3] = 1.0f;
+        sc_s.manual_exposure = p.manual_exposure;
+        sc_s.draw_begin = d0;
+        sc_s.draw_end = d0 + nd_total;
+        sc_s.n_prims = prim_total;
 #pragma unroll
         for (int i = 0; i < 16; ++i) scenes[s].camera_pose[i] = cam[i];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ea.env_out[(size_t)s * 3 + k] = env_id[k];
     }
     __syncthreads();
     copy16(out_scenes + s, &sc_s, sizeof(slhip_scene), lane, 64);
@@ -600,6 +729,15 @@ __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const 
         dr.base_color[0] = 0.0f; dr.base_color[1] = 0.8f; dr.base_color[2] = 0.0f; dr.base_color[3] = 1.0f;
         dr.alpha_cutoff = 0.5f; dr.metallic = 0.04f; dr.roughness = 0.5f;
         dr.scene = local; dr.flags = SLHIP_DRAW_NO_VERTEX_ID;
+        if constexpr (kEnv) {
+            if (env_id[2] >= 0) {       // RenderShader::setMaterial with a base texture (render_pass.cpp:559-575)
+                const slhip_env_texture t = ea.env.d_plane_textures[env_id[2]];
+                dr.base_color[0] = 1.0f; dr.base_color[1] = 1.0f; dr.base_color[2] = 1.0f;
+                dr.tex_offset = t.offset; dr.tex_w = t.w; dr.tex_h = t.h;
+                dr.tex_sampler[0] = (uint8_t)t.sampler;
+                dr.flags |= SLHIP_DRAW_HAS_BASE_TEX;
+            }
+        }
         dr.n_verts = 4; dr.n_tris = 2; dr.prim_base = 0; dr.clip_base = clip_base_scene;
         draws[0] = dr;
         slhip_chunk ck;
@@ -678,6 +816,9 @@ static_assert(sizeof(slhip_asset) == 224, "slhip_asset layout");
 static_assert(sizeof(slhip_synth_params) == 224, "slhip_synth_params layout");
 static_assert(sizeof(slhip_synth_object) == 16, "slhip_synth_object layout");
 static_assert(sizeof(slhip_synth_scene) == 128, "slhip_synth_scene layout");
+static_assert(sizeof(slhip_env_light_set) == 112, "slhip_env_light_set layout");
+static_assert(sizeof(slhip_env_texture) == 16, "slhip_env_texture layout");
+static_assert(sizeof(slhip_synth_env) == 56, "slhip_synth_env layout");
 static_assert(sizeof(slhip_draw) % 16 == 0 && sizeof(slhip_scene) % 16 == 0, "records are copied in 16-byte units");
 
 extern "C" int slhip_synth_stage(const slhip_synth_params* params, const slhip_asset* d_assets, const uint16_t* d_asset_ids,
@@ -721,8 +862,60 @@ extern "C" int slhip_synth_place(const slhip_synth_params* params, const slhip_a
         return -1;
     }
     if (params->n_scenes == 0) return 0;
-    k_synth_place<<<params->n_scenes, 64, 0, (hipStream_t)stream>>>(*params, d_assets, d_templates, d_bodies, d_objects,
-                                                                    d_scenes, d_out_scenes, d_out_draws, d_out_chunks);
+    k_synth_place<false><<<params->n_scenes, 64, 0, (hipStream_t)stream>>>(*params, d_assets, d_templates, d_bodies, d_objects,
+                                                                           d_scenes, d_out_scenes, d_out_draws, d_out_chunks,
+                                                                           no_env_args{});
+    SLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int slhip_synth_place_env(const slhip_synth_params* params, const slhip_synth_env* env, const slhip_asset* d_assets,
+                                     const slhip_draw* d_templates, const slhip_body* d_bodies,
+                                     const slhip_synth_object* d_objects, slhip_synth_scene* d_scenes, slhip_scene* d_out_scenes,
+                                     slhip_draw* d_out_draws, slhip_chunk* d_out_chunks, int32_t* d_env_out, void* stream)
+{
+    const char* what = "slhip_synth_place_env";
+    if (int st = check_params(params, what)) return st;
+    if (!env) {
+        slhip::set_error("%s: null environment", what);
+        return -1;
+    }
+    const struct { const char* name; const void* bank; uint32_t n; float prob; } kinds[3] = {
+        {"light_sets / p_light_map", env->d_light_sets, env->n_light_sets, env->p_light_map},
+        {"backgrounds / p_background", env->d_backgrounds, env->n_backgrounds, env->p_background},
+        {"plane_textures / p_plane_texture", env->d_plane_textures, env->n_plane_textures, env->p_plane_texture}};
+    for (const auto& k : kinds) {
+        if (k.n > 0 && !k.bank) {
+            slhip::set_error("%s: %s: %u entries but a null bank", what, k.name, k.n);
+            return -1;
+        }
+        if (!(k.prob >= 0.0f && k.prob <= 1.0f)) {      // false for NaN as well
+            slhip::set_error("%s: %s: the probability must be in [0, 1]", what, k.name);
+            return -1;
+        }
+        if (!env->d_env_ids && k.prob > 0.0f && k.n == 0) {
+            slhip::set_error("%s: %s: a probability above zero needs a bank that is not empty", what, k.name);
+            return -1;
+        }
+    }
+    if (!d_env_out) {
+        slhip::set_error("%s: null d_env_out", what);
+        return -1;
+    }
+    if (!d_assets || !d_templates || !d_bodies || !d_objects || !d_scenes || !d_out_scenes || !d_out_draws || !d_out_chunks) {
+        slhip::set_error("%s: null argument", what);
+        return -1;
+    }
+    if (params->max_draws_per_scene == 0 || params->max_chunks_per_scene == 0) {
+        slhip::set_error("%s: record strides (max_draws_per_scene, max_chunks_per_scene) must be set", what);
+        return -1;
+    }
+    if (params->n_scenes == 0) return 0;
+    env_args ea;
+    ea.env = *env;
+    ea.env_out = d_env_out;
+    k_synth_place<true><<<params->n_scenes, 64, 0, (hipStream_t)stream>>>(*params, d_assets, d_templates, d_bodies, d_objects,
+                                                                          d_scenes, d_out_scenes, d_out_draws, d_out_chunks, ea);
     SLHIP_LAUNCH_CHECK();
     return 0;
 }

@@ -11,6 +11,12 @@ camera intrinsics, light colour, seed); per scene nothing crosses PCIe.
     batch.stage(); batch.settle(); batch.place()
     for chunk in batch.render_chunks(): ...             # RenderBuffers, [chunk, H, W, C] tensors in HBM
     scene = batch.scene(17)                             # an ordinary sl.Scene rebuilt from the device records
+
+Domain randomisation of the picture (examples/ycb.py --ibl / --plane-texture, Scene.background_image): an
+sl.EnvironmentBank of light maps, background images and plane textures, handed out per scene by the place step:
+
+    bank = sl.EnvironmentBank(light_maps, backgrounds, plane_textures)          # once
+    batch = sl.SceneBatch(table, 4096, 20, environment=bank, p_light_map=0.5)
 """
 import ctypes as C
 import os
@@ -118,11 +124,24 @@ class AssetTable:
 class SceneBatch:
     """n_scenes tabletop scenes of n_objects objects each, resident in HBM.  `asset_ids` ([n_scenes, n_objects]
     class indices into the table) fixes every scene's objects; without it each scene draws n_objects DISTINCT
-    classes (examples/ycb.py:60).  `random_pbr`: metallic / roughness ~ U(0,1) per object (examples/ycb.py:63-64)."""
+    classes (examples/ycb.py:60).  `random_pbr`: metallic / roughness ~ U(0,1) per object (examples/ycb.py:63-64).
+
+    `environment`: an sl.EnvironmentBank.  place() then gives every scene a light map with probability `p_light_map`, a
+    background image with `p_background` and a plane texture with `p_plane_texture`, each picked uniformly from the bank
+    with the batch's counter-based random streams (stream 4 of include/slhip.h; the probability of a kind the bank has no
+    entry of is not used) -- or exactly what `env_ids` ([n_scenes, 3] = light set, background, plane texture; -1 = none)
+    names.  A scene with a light map is lit by the map and the map's lights, without ambient term, as `scene.light_map`
+    does it on the per-scene path; the others keep the drawn light.  host_env() tells what every scene got.
+
+    Memory: the render scratch holds one 2048 x 2048 f32 shadow map per scene and LIGHT, 16.8 MB each, and a batch on a bank
+    renders with as many as the bank's largest light set has (at least 1): a 512-scene render chunk takes 8.6 GB of shadow
+    maps with one-light maps and 25.8 GB with three-light maps.  The engine checks the free memory before it allocates;
+    choose `render_chunk` accordingly."""
 
     def __init__(self, table, n_scenes, n_objects, resolution=(640, 480), seed=0, asset_ids=None, random_pbr=True,
                  shadows=True, render_chunk=None, plane_size=(3.0, 3.0), light_color=(300.0, 300.0, 300.0),
-                 ambient=(0.05, 0.05, 0.05), manual_exposure=-1.0, scene_id_base=0, pair_contact_budget=SB.PAIR_CONTACT_BUDGET):
+                 ambient=(0.05, 0.05, 0.05), manual_exposure=-1.0, scene_id_base=0, pair_contact_budget=SB.PAIR_CONTACT_BUDGET,
+                 environment=None, p_light_map=1.0, p_background=1.0, p_plane_texture=1.0, env_ids=None):
         from .scene import Scene
 
         if not 1 <= n_objects <= 64:      # SLHIP_SYNTH_MAX_OBJECTS: the synthesis kernels map an object to a lane of one wave
@@ -190,6 +209,27 @@ class SceneBatch:
         self.d_drec = buf(self.n_scenes * int(p["max_draws_per_scene"]) * _abi.DRAW_DTYPE.itemsize)
         self.d_crec = buf(self.n_scenes * int(p["max_chunks_per_scene"]) * _abi.CHUNK_DTYPE.itemsize)
         self.d_asset_ids = None if self.asset_ids is None else torch.from_numpy(self.asset_ids.view(np.int16).copy()).to(dev)
+        # environment bank (slhip_synth_place_env)
+        self.environment, self.env_ids, self.d_env_ids, self.d_env_out = environment, None, None, None
+        if environment is None:
+            if env_ids is not None:
+                raise ValueError("env_ids needs an environment bank")
+        else:
+            if environment.eng is not self.eng:
+                raise ValueError("the environment bank and the asset table must live on the same device engine")
+            counts = environment.counts()
+            probs = [float(p_light_map), float(p_background), float(p_plane_texture)]
+            for name, pr in zip(("p_light_map", "p_background", "p_plane_texture"), probs):
+                if not 0.0 <= pr <= 1.0:             # (false for NaN)
+                    raise ValueError("%s must be in [0, 1]" % name)
+            self.env_probs = tuple(pr if n else 0.0 for pr, n in zip(probs, counts))
+            if env_ids is not None:
+                ids = np.ascontiguousarray(env_ids, dtype=np.int32).reshape(self.n_scenes, 3)
+                if (ids < -1).any() or (ids >= np.array(counts, np.int32)[None, :]).any():
+                    raise ValueError("environment id out of range")
+                self.env_ids = ids
+                self.d_env_ids = torch.from_numpy(ids.copy()).to(dev)
+            self.d_env_out = torch.full((self.n_scenes, 3), -1, dtype=torch.int32, device=dev)
 
     # ---- camera (shared by all scenes of the batch; sl.Scene's setters) --------------------------------------
     def _set_projection(self):
@@ -264,9 +304,24 @@ class SceneBatch:
         return self.se.caps(self.n_scenes, self._settle_stream, self._settle_keep)
 
     def place(self):
-        """Camera pose, light direction, shadow matrix and the render records of every scene."""
+        """Camera pose, light direction, shadow matrix and the render records of every scene; with an environment bank also
+        every scene's light map / background image / plane texture and the shadow matrices of all its lights."""
         d_assets, d_templates = self.table.device()
         stream = torch.cuda.current_stream(self.eng.device).cuda_stream
+        if self.environment is not None:
+            d_ls, d_bg, d_pt = self.environment.device()
+            e = _abi.SynthEnv()
+            e.d_light_sets, e.d_backgrounds, e.d_plane_textures = d_ls.data_ptr(), d_bg.data_ptr(), d_pt.data_ptr()
+            e.d_env_ids = self.d_env_ids.data_ptr() if self.d_env_ids is not None else None
+            e.n_light_sets, e.n_backgrounds, e.n_plane_textures = self.environment.counts()
+            e.p_light_map, e.p_background, e.p_plane_texture = self.env_probs
+            with torch.cuda.device(self.eng.device):
+                st = self.eng.L.slhip_synth_place_env(self._p(), C.byref(e), self._a(d_assets), self._a(d_templates),
+                                                      self._a(self.d_bodies), self._a(self.d_objects), self._a(self.d_scenes),
+                                                      self._a(self.d_srec), self._a(self.d_drec), self._a(self.d_crec),
+                                                      self._a(self.d_env_out), C.c_void_p(stream))
+            _abi.check(st, "slhip_synth_place_env")
+            return
         with torch.cuda.device(self.eng.device):
             st = self.eng.L.slhip_synth_place(self._p(), self._a(d_assets), self._a(d_templates), self._a(self.d_bodies),
                                               self._a(self.d_objects), self._a(self.d_scenes), self._a(self.d_srec),
@@ -296,7 +351,8 @@ class SceneBatch:
             self.d_drec.data_ptr() + s0 * md * _abi.DRAW_DTYPE.itemsize,
             self.d_crec.data_ptr() + s0 * mk * _abi.CHUNK_DTYPE.itemsize,
             B, B * md, B * mk, B * mv, W, H, mask, ssao=ssao, shadows=self.shadows, buffers=buffers,
-            shadow_lights=1,       # the synthesised scenes have one light (k_synth_place)
+            # the synthesised scenes have one light, or as many as the largest light set of the bank (k_synth_place)
+            shadow_lights=1 if self.environment is None else max(1, self.environment.max_lights),
             object_stats=object_stats, n_slots=self.n_objects + 1)   # instance index = object + 1 (k_synth_place)
 
     def render_chunks(self, mask=_abi.OUT_GT6, ssao=True, object_stats=False):
@@ -325,9 +381,16 @@ class SceneBatch:
                 self._host(self.d_drec, _abi.DRAW_DTYPE, self.n_scenes * md),
                 self._host(self.d_crec, _abi.CHUNK_DTYPE, self.n_scenes * mk))
 
+    def host_env(self):
+        """[n_scenes, 3] int32: the (light set, background, plane texture) of the bank every scene got at place(); -1 = none."""
+        if self.environment is None:
+            return np.full((self.n_scenes, 3), -1, np.int32)
+        return self.d_env_out.cpu().numpy().copy()
+
     def scene(self, index, _cache=None):
-        """Scene `index` as an ordinary sl.Scene (objects, poses, velocities, camera, light, plane) rebuilt from the
-        device records -- the hand-over to the per-scene API (serialize, render with other settings, ...)."""
+        """Scene `index` as an ordinary sl.Scene (objects, poses, velocities, camera, light, plane, and the light map /
+        background image / plane texture it got from the environment bank) rebuilt from the device records -- the hand-over
+        to the per-scene API (serialize, render with other settings, ...)."""
         from .object import Object
         from .scene import Scene
 
@@ -357,4 +420,10 @@ class SceneBatch:
         scene._light_colors[0] = torch.from_numpy(np.asarray(self.params["light_color"][:3], np.float32).copy())
         scene._ambient_light = np.asarray(self.params["ambient"][:3], np.float32).copy()
         scene._manual_exposure = f32(self.params["manual_exposure"])
+        if self.environment is not None:
+            ids = c.get("env") if "env" in c else self.host_env()
+            li, bi, ti = (int(v) for v in ids[index])
+            scene._light_map = self.environment.light_map(li)
+            scene._background_image = self.environment.background(bi)
+            scene._background_plane_texture = self.environment.plane_texture(ti)
         return scene

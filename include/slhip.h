@@ -638,6 +638,10 @@ int slhip_stream_destroy(void* stream);
  * roughness, 4 environment (slhip_synth_place_env only; no draw of streams 0-3 depends on it).  Stream 4, index 0:
  * x[0] gates the light set, x[1] picks it, x[2] gates the background image, x[3] picks it; index 1: x[0] gates the plane
  * texture, x[1] picks it.  Gate: uniform(x) < p.  Pick: min(n - 1, (uint32_t)(uniform(x) * (float)n)), float32 throughout.
+ * Views (slhip_synth_place_view): azimuth and elevation of view v >= 1 are the draw of view 0 -- stream 0, index 0, words 1 and
+ * 2, the same scene id, the same formulas -- under the key (seed_lo + v * 0x9E3779B9, seed_hi + v * 0xBB67AE85), each sum
+ * wrapping at 32 bits.  No other draw uses the view's key: the light's normals, the environment's gates and picks and everything
+ * of slhip_synth_stage keep the batch's key in every view.
  * ------------------------------------------------------------------------------------------- */
 
 /* One mesh class: what sl.Mesh (+ the defaults of sl.Object) contributes to a scene. */
@@ -753,6 +757,32 @@ int slhip_synth_place_env(const slhip_synth_params* params, const slhip_synth_en
                           const slhip_draw* d_templates, const slhip_body* d_bodies, const slhip_synth_object* d_objects,
                           slhip_synth_scene* d_scenes, slhip_scene* d_out_scenes, slhip_draw* d_out_draws,
                           slhip_chunk* d_out_chunks, int32_t* d_env_out, void* stream);
+
+/* Another camera on the SAME settled scenes: a view.  Poses, lights, environment, every slhip_draw and slhip_chunk and
+ * light_color / ambient / light_map / bg_tex of slhip_scene carry the bits slhip_synth_place (env NULL) or
+ * slhip_synth_place_env writes; world_to_cam, cam_position, shadow_mat[*] and slhip_synth_scene.camera_pose are the view's
+ * (camera_pose is overwritten: a hand-over sees the view placed last).  The shadow matrices are fitted to the view's frustum
+ * by the arithmetic of slhip_synth_place (render_pass.cpp:69-211 runs per render).  A scene without a light set keeps, in
+ * every view, the world-space light_dir slhip_synth_place writes for it: the reference draws the light in the camera frame,
+ * and the scene's camera is view 0's (scene.cpp:453-470).  View 0 without d_camera_poses is slhip_synth_place /
+ * slhip_synth_place_env bit for bit. */
+typedef struct {
+    uint32_t view;                /* 0: the camera slhip_synth_place gives the scene.  v >= 1: the same draw under the key
+                                     of view v ("Randomness"), the same fit to the objects (scene.cpp:472-610)            */
+    uint32_t _pad;
+    const float* d_camera_poses;  /* NULL, or [n_scenes][16] camera-to-world, row-major (Scene::cameraPose): taken as it
+                                     is -- no draw, no fit; `view` is ignored.  A pose with an entry that is not finite
+                                     makes the scene EMPTY (no draws -- as for record strides that do not fit) under
+                                     the identity camera                                                                */
+    float* d_object_to_camera;    /* NULL, or out [n_scenes][n_objects][12]: rows of world_to_cam * pose (3x4)             */
+} slhip_synth_view;         /* 24 bytes */
+
+/* env NULL: the plain form (d_env_out NULL as well); else the form of slhip_synth_place_env with its refusals.  Refused
+ * before any launch besides: a null view; d_env_out and env not both null or both set.                               */
+int slhip_synth_place_view(const slhip_synth_params* params, const slhip_synth_env* env, const slhip_synth_view* view,
+                           const slhip_asset* d_assets, const slhip_draw* d_templates, const slhip_body* d_bodies,
+                           const slhip_synth_object* d_objects, slhip_synth_scene* d_scenes, slhip_scene* d_out_scenes,
+                           slhip_draw* d_out_draws, slhip_chunk* d_out_chunks, int32_t* d_env_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Host side of the per-object API (sl.Scene / sl.RenderPass): record assembly in C++, one call per batch.

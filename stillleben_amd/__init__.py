@@ -23,12 +23,14 @@ from .scene_batch import AssetTable, SceneBatch  # noqa: F401  (additive: the ba
 from .environment import EnvironmentBank  # noqa: F401  (additive: light maps / backgrounds / plane textures of a SceneBatch)
 from .object_stats import ObjectStats  # noqa: F401  (additive: per-object visibility statistics, BOP's scene_gt_info)
 from . import camera_model, diff, losses, extension, profiling  # noqa: F401
+from . import bop  # noqa: F401  (additive: BOP scene_camera / scene_gt entries from a SceneBatch's records)
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
     'Mesh', 'MeshCache', 'Object', 'Range3D', 'RenderPass', 'RenderPassResult', 'Scene', 'Texture',
     'Texture2D', 'Viewer', 'view', 'ManipulationSim', 'JobQueue', 'AssetTable', 'SceneBatch',
     'camera_model', 'diff', 'extension', 'losses', 'quat_to_matrix', 'matrix_to_quat', 'ObjectStats', 'EnvironmentBank',
+    'bop',
 ]
 
 

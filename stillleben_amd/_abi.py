@@ -246,7 +246,29 @@ class SynthEnv(C.Structure):
 
 
 assert C.sizeof(SynthEnv) == 56
-SYNTH_STREAM_ENV = 4      # Philox stream of the environment draws (include/slhip.h, "Randomness")
+
+
+class SynthView(C.Structure):
+    """slhip_synth_view: which camera slhip_synth_place_view gives the scenes."""
+
+    _fields_ = [
+        ("view", C.c_uint32),
+        ("_pad", C.c_uint32),
+        ("d_camera_poses", C.c_void_p),
+        ("d_object_to_camera", C.c_void_p),
+    ]
+
+
+assert C.sizeof(SynthView) == 24
+VIEW_KEY_STEP = (0x9E3779B9, 0xBB67AE85)      # Philox key of view v: (seed_lo + v * step[0], seed_hi + v * step[1]) mod 2^32
+
+
+def view_key(seed_lo, seed_hi, view):
+    """The Philox key azimuth and elevation of view `view` are drawn with (include/slhip.h, "Randomness")."""
+    return ((int(seed_lo) + int(view) * VIEW_KEY_STEP[0]) & 0xFFFFFFFF, (int(seed_hi) + int(view) * VIEW_KEY_STEP[1]) & 0xFFFFFFFF)
+
+
+SYNTH_STREAM_ENV = 4     # Philox stream of the environment draws (include/slhip.h, "Randomness")
 SYNTH_SAMPLE_DISTINCT = 1
 SYNTH_RANDOM_PBR = 2
 SYNTH_SHADOWS = 4
@@ -329,6 +351,8 @@ def lib():
     L.slhip_synth_place.argtypes = [C.c_void_p] * 10
     if hasattr(L, "slhip_synth_place_env"):          # (absent from older builds selected through SLHIP_LIB for A/B runs)
         L.slhip_synth_place_env.argtypes = [C.c_void_p, C.POINTER(SynthEnv)] + [C.c_void_p] * 10
+    if hasattr(L, "slhip_synth_place_view"):
+        L.slhip_synth_place_view.argtypes = [C.c_void_p, C.POINTER(SynthEnv), C.POINTER(SynthView)] + [C.c_void_p] * 10
     L.slhip_comm_unique_id.argtypes = [C.c_void_p]
     L.slhip_comm_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.slhip_comm_destroy.argtypes = [C.c_void_p]

@@ -439,20 +439,38 @@ struct env_args {
     int32_t* env_out;
 };
 struct no_env_args {};
-template <bool kEnv> struct place_env { typedef no_env_args type; };
-template <> struct place_env<true> { typedef env_args type; };
+// ... and what the view form gets on top of either (slhip_synth_place_view)
+struct view_args : no_env_args { slhip_synth_view view; };
+struct env_view_args : env_args { slhip_synth_view view; };
+template <bool kEnv, bool kView> struct place_env { typedef no_env_args type; };
+template <> struct place_env<true, false> { typedef env_args type; };
+template <> struct place_env<false, true> { typedef view_args type; };
+template <> struct place_env<true, true> { typedef env_view_args type; };
+
+// Rotation of the camera at (azimuth, elevation): scene.cpp:489-493
+__device__ __forceinline__ void camera_rotation(float azimuth, float elevation, float* cam_rot)
+{
+    float rz[16], ry[16], t0[16];
+    const float C[16] = {0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 1};
+    rot_z(azimuth, rz);
+    rot_y(elevation, ry);
+    mm4(rz, ry, t0);
+    mm4(t0, C, cam_rot);
+}
 
 // kEnv = false: the record slhip_synth_place has always written (one drawn light, green plane, cleared background).
 // kEnv = true: every scene additionally takes a light set / background image / plane texture of the environment bank, drawn
 // from STREAM_ENV or named by d_env_ids, and every active light gets its shadow matrix.
-template <bool kEnv>
+// kView = true (slhip_synth_place_view): the camera is another view's -- azimuth / elevation drawn with the view's key, or the
+// caller's pose --, the drawn light stays the one view 0's camera frame gives, object lanes may write world_to_cam * pose.
+template <bool kEnv, bool kView = false>
 __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const slhip_asset* __restrict__ assets,
                                                    const slhip_draw* __restrict__ templates,
                                                    const slhip_body* __restrict__ bodies_all,
                                                    const slhip_synth_object* __restrict__ objects_all,
                                                    slhip_synth_scene* __restrict__ scenes, slhip_scene* __restrict__ out_scenes,
                                                    slhip_draw* __restrict__ out_draws, slhip_chunk* __restrict__ out_chunks,
-                                                   typename place_env<kEnv>::type ea)
+                                                   typename place_env<kEnv, kView>::type ea)
 {
     __shared__ slhip_scene sc_s;
     __shared__ uint32_t obj_nd[SLHIP_SYNTH_MAX_OBJECTS + 1], obj_nk[SLHIP_SYNTH_MAX_OBJECTS + 1];
@@ -477,18 +495,29 @@ __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const 
 
     uint32_t x[4];
     draw4(p, s, STREAM_SCENE, 0, x);
-    const float azimuth = fmaf(u01(x[1]), kTwoPi, -kPi);
-    const float elevation = fmaf(u01(x[2]), kElevSpan, kElevSpan);
+    float azimuth = fmaf(u01(x[1]), kTwoPi, -kPi);
+    float elevation = fmaf(u01(x[2]), kElevSpan, kElevSpan);
+    // kView: the frame the light is drawn in is view 0's camera (its rotation: the translation of the fit does not enter the
+    // 3x3 part of cam_rot * translation); then the view's own azimuth / elevation, same counter, the view's key
+    float cam0[16];
+    if constexpr (kView) {
+        float cam_rot[16], tr[16];
+        camera_rotation(azimuth, elevation, cam_rot);
+        translation4(0.0f, 0.0f, 0.0f, tr);
+        mm4(cam_rot, tr, cam0);
+        if (ea.view.view != 0) {
+            philox(p.scene_id_base + s, STREAM_SCENE, 0, 0x51DE5EEDu, p.seed_lo + ea.view.view * 0x9E3779B9u,
+                   p.seed_hi + ea.view.view * 0xBB67AE85u, x);
+            azimuth = fmaf(u01(x[1]), kTwoPi, -kPi);
+            elevation = fmaf(u01(x[2]), kElevSpan, kElevSpan);
+        }
+    }
 
     // ---- camera pose (scene.cpp:472-610) ----
     float cam[16];
     {
-        float rz[16], ry[16], t0[16], cam_rot[16], to_work[16];
-        const float C[16] = {0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 1};
-        rot_z(azimuth, rz);
-        rot_y(elevation, ry);
-        mm4(rz, ry, t0);
-        mm4(t0, C, cam_rot);
+        float cam_rot[16], to_work[16];
+        camera_rotation(azimuth, elevation, cam_rot);
         inv_rigid(cam_rot, to_work);
         float fr[4][4];
 #pragma unroll
@@ -533,6 +562,15 @@ __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const 
         translation4(lr_x, tb_y, fminf(lr_z, tb_z), tr);
         mm4(cam_rot, tr, cam);
     }
+    bool cam_ok = true;         // wave-uniform
+    if constexpr (kView) {
+        if (ea.view.d_camera_poses) {      // the caller's camera, as it is; a pose that is not finite: the scene is written EMPTY
+#pragma unroll
+            for (int i = 0; i < 16; ++i) cam[i] = ea.view.d_camera_poses[(size_t)s * 16 + i];
+            cam_ok = finite16(cam);
+            if (!cam_ok) identity4(cam);       // (the records of the empty scene stay finite)
+        }
+    }
     float w2c[16], c2w[16];
     inv_rigid(cam, w2c);
     inv_rigid(w2c, c2w);
@@ -548,11 +586,13 @@ __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const 
         normalize3(d);
         normalize3(d);
         const float lc[3] = {-d[0], -d[1], -d[2]};
+        const float* lf = cam;
+        if constexpr (kView) lf = cam0;
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
-            float t = fmaf(cam[4 * r + 0], lc[0], 0.0f);
-            t = fmaf(cam[4 * r + 1], lc[1], t);
-            t = fmaf(cam[4 * r + 2], lc[2], t);
+            float t = fmaf(lf[4 * r + 0], lc[0], 0.0f);
+            t = fmaf(lf[4 * r + 1], lc[1], t);
+            t = fmaf(lf[4 * r + 2], lc[2], t);
             ld[r] = t;
         }
     }
@@ -668,7 +708,7 @@ __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const 
     const uint32_t d0 = local * p.max_draws_per_scene;
     // strides too small for this scene (a host error: the strides come from the asset table's maxima): write the
     // scene EMPTY rather than out of bounds -- an all-background image is impossible to miss
-    const bool fits = nd_total <= p.max_draws_per_scene && nk_total <= p.max_chunks_per_scene && env_ok;
+    const bool fits = nd_total <= p.max_draws_per_scene && nk_total <= p.max_chunks_per_scene && env_ok && cam_ok;
     if (!fits) { nd_total = 0; nk_total = 0; prim_total = 0; }
     slhip_draw* draws = out_draws + (size_t)s * p.max_draws_per_scene;
     slhip_chunk* chunks = out_chunks + (size_t)s * p.max_chunks_per_scene;
@@ -712,6 +752,15 @@ __global__ __launch_bounds__(64) void k_synth_place(slhip_synth_params p, const 
     }
     __syncthreads();
     copy16(out_scenes + s, &sc_s, sizeof(slhip_scene), lane, 64);
+    if constexpr (kView) {
+        if (ea.view.d_object_to_camera && has_obj) {      // rows 0-2 of world_to_cam * pose
+            float o2c[16];
+            mm4(w2c, pose, o2c);
+            float* dst = ea.view.d_object_to_camera + ((size_t)s * p.n_objects + lane) * 12;
+#pragma unroll
+            for (int i = 0; i < 12; ++i) dst[i] = o2c[i];
+        }
+    }
 
     // ---- background plane (render_pass.cpp:545-582): lane 63 (never an object lane's job when n_objects < 64) ----
     if (fits && has_plane && lane == 63) {
@@ -810,6 +859,33 @@ int check_params(const slhip_synth_params* p, const char* what)
     return 0;
 }
 
+int check_env(const slhip_synth_env* env, const char* what)
+{
+    if (!env) {
+        slhip::set_error("%s: null environment", what);
+        return -1;
+    }
+    const struct { const char* name; const void* bank; uint32_t n; float prob; } kinds[3] = {
+        {"light_sets / p_light_map", env->d_light_sets, env->n_light_sets, env->p_light_map},
+        {"backgrounds / p_background", env->d_backgrounds, env->n_backgrounds, env->p_background},
+        {"plane_textures / p_plane_texture", env->d_plane_textures, env->n_plane_textures, env->p_plane_texture}};
+    for (const auto& k : kinds) {
+        if (k.n > 0 && !k.bank) {
+            slhip::set_error("%s: %s: %u entries but a null bank", what, k.name, k.n);
+            return -1;
+        }
+        if (!(k.prob >= 0.0f && k.prob <= 1.0f)) {      // false for NaN as well
+            slhip::set_error("%s: %s: the probability must be in [0, 1]", what, k.name);
+            return -1;
+        }
+        if (!env->d_env_ids && k.prob > 0.0f && k.n == 0) {
+            slhip::set_error("%s: %s: a probability above zero needs a bank that is not empty", what, k.name);
+            return -1;
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 static_assert(sizeof(slhip_asset) == 224, "slhip_asset layout");
@@ -819,6 +895,7 @@ static_assert(sizeof(slhip_synth_scene) == 128, "slhip_synth_scene layout");
 static_assert(sizeof(slhip_env_light_set) == 112, "slhip_env_light_set layout");
 static_assert(sizeof(slhip_env_texture) == 16, "slhip_env_texture layout");
 static_assert(sizeof(slhip_synth_env) == 56, "slhip_synth_env layout");
+static_assert(sizeof(slhip_synth_view) == 24, "slhip_synth_view layout");
 static_assert(sizeof(slhip_draw) % 16 == 0 && sizeof(slhip_scene) % 16 == 0, "records are copied in 16-byte units");
 
 extern "C" int slhip_synth_stage(const slhip_synth_params* params, const slhip_asset* d_assets, const uint16_t* d_asset_ids,
@@ -876,28 +953,7 @@ extern "C" int slhip_synth_place_env(const slhip_synth_params* params, const slh
 {
     const char* what = "slhip_synth_place_env";
     if (int st = check_params(params, what)) return st;
-    if (!env) {
-        slhip::set_error("%s: null environment", what);
-        return -1;
-    }
-    const struct { const char* name; const void* bank; uint32_t n; float prob; } kinds[3] = {
-        {"light_sets / p_light_map", env->d_light_sets, env->n_light_sets, env->p_light_map},
-        {"backgrounds / p_background", env->d_backgrounds, env->n_backgrounds, env->p_background},
-        {"plane_textures / p_plane_texture", env->d_plane_textures, env->n_plane_textures, env->p_plane_texture}};
-    for (const auto& k : kinds) {
-        if (k.n > 0 && !k.bank) {
-            slhip::set_error("%s: %s: %u entries but a null bank", what, k.name, k.n);
-            return -1;
-        }
-        if (!(k.prob >= 0.0f && k.prob <= 1.0f)) {      // false for NaN as well
-            slhip::set_error("%s: %s: the probability must be in [0, 1]", what, k.name);
-            return -1;
-        }
-        if (!env->d_env_ids && k.prob > 0.0f && k.n == 0) {
-            slhip::set_error("%s: %s: a probability above zero needs a bank that is not empty", what, k.name);
-            return -1;
-        }
-    }
+    if (int st = check_env(env, what)) return st;
     if (!d_env_out) {
         slhip::set_error("%s: null d_env_out", what);
         return -1;
@@ -916,6 +972,50 @@ extern "C" int slhip_synth_place_env(const slhip_synth_params* params, const slh
     ea.env_out = d_env_out;
     k_synth_place<true><<<params->n_scenes, 64, 0, (hipStream_t)stream>>>(*params, d_assets, d_templates, d_bodies, d_objects,
                                                                           d_scenes, d_out_scenes, d_out_draws, d_out_chunks, ea);
+    SLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int slhip_synth_place_view(const slhip_synth_params* params, const slhip_synth_env* env, const slhip_synth_view* view,
+                                      const slhip_asset* d_assets, const slhip_draw* d_templates, const slhip_body* d_bodies,
+                                      const slhip_synth_object* d_objects, slhip_synth_scene* d_scenes,
+                                      slhip_scene* d_out_scenes, slhip_draw* d_out_draws, slhip_chunk* d_out_chunks,
+                                      int32_t* d_env_out, void* stream)
+{
+    const char* what = "slhip_synth_place_view";
+    if (int st = check_params(params, what)) return st;
+    if (!view) {
+        slhip::set_error("%s: null view", what);
+        return -1;
+    }
+    if (env)
+        if (int st = check_env(env, what)) return st;
+    if ((env != nullptr) != (d_env_out != nullptr)) {
+        slhip::set_error("%s: d_env_out goes with env: both null or both set", what);
+        return -1;
+    }
+    if (!d_assets || !d_templates || !d_bodies || !d_objects || !d_scenes || !d_out_scenes || !d_out_draws || !d_out_chunks) {
+        slhip::set_error("%s: null argument", what);
+        return -1;
+    }
+    if (params->max_draws_per_scene == 0 || params->max_chunks_per_scene == 0) {
+        slhip::set_error("%s: record strides (max_draws_per_scene, max_chunks_per_scene) must be set", what);
+        return -1;
+    }
+    if (params->n_scenes == 0) return 0;
+    if (env) {
+        env_view_args ea;
+        ea.env = *env;
+        ea.env_out = d_env_out;
+        ea.view = *view;
+        k_synth_place<true, true><<<params->n_scenes, 64, 0, (hipStream_t)stream>>>(
+            *params, d_assets, d_templates, d_bodies, d_objects, d_scenes, d_out_scenes, d_out_draws, d_out_chunks, ea);
+    } else {
+        view_args va;
+        va.view = *view;
+        k_synth_place<false, true><<<params->n_scenes, 64, 0, (hipStream_t)stream>>>(
+            *params, d_assets, d_templates, d_bodies, d_objects, d_scenes, d_out_scenes, d_out_draws, d_out_chunks, va);
+    }
     SLHIP_LAUNCH_CHECK();
     return 0;
 }

@@ -17,6 +17,11 @@ sl.EnvironmentBank of light maps, background images and plane textures, handed o
 
     bank = sl.EnvironmentBank(light_maps, backgrounds, plane_textures)          # once
     batch = sl.SceneBatch(table, 4096, 20, environment=bank, p_light_map=0.5)
+
+Several pictures of one settled scene (a BOP scene: one pile, many images; sl.bop writes the entries):
+
+    for v, chunk, buffers in batch.views(8): ...        # view 0 = the camera of place(); v >= 1 further drawn cameras
+    batch.place(camera_poses=poses)                      # or the caller's cameras, [n_scenes, 4, 4] on the device
 """
 import ctypes as C
 import os
@@ -38,6 +43,20 @@ def _dev(arr, device):
     if raw.size == 0:
         raw = np.zeros(16, np.uint8)
     return torch.from_numpy(raw.copy()).to(device)
+
+
+def check_view_arguments(view, camera_poses, n_scenes, device):
+    """The argument errors of SceneBatch.place(view=, camera_poses=): raised before anything is asked of the device."""
+    if isinstance(view, bool) or int(view) != view or not 0 <= int(view) <= 0xFFFFFFFF:
+        raise ValueError("view must be an integer in [0, 2^32)")
+    if camera_poses is None:
+        return
+    if not isinstance(camera_poses, torch.Tensor) or camera_poses.dtype != torch.float32:
+        raise ValueError("camera_poses must be a float32 torch tensor")
+    if tuple(camera_poses.shape) != (int(n_scenes), 4, 4) or not camera_poses.is_contiguous():
+        raise ValueError("camera_poses must be a contiguous [n_scenes, 4, 4] = [%d, 4, 4] tensor" % n_scenes)
+    if camera_poses.device != torch.device(device):
+        raise ValueError("camera_poses must live on the batch's device (%s), not on %s" % (device, camera_poses.device))
 
 
 class AssetTable:
@@ -136,7 +155,8 @@ class SceneBatch:
     Memory: the render scratch holds one 2048 x 2048 f32 shadow map per scene and LIGHT, 16.8 MB each, and a batch on a bank
     renders with as many as the bank's largest light set has (at least 1): a 512-scene render chunk takes 8.6 GB of shadow
     maps with one-light maps and 25.8 GB with three-light maps.  The engine checks the free memory before it allocates;
-    choose `render_chunk` accordingly."""
+    choose `render_chunk` accordingly.  Further views (place(view=...), views()) overwrite the one record set and render into
+    the same scratch: they add nothing to this, object_to_camera 48 bytes per object."""
 
     def __init__(self, table, n_scenes, n_objects, resolution=(640, 480), seed=0, asset_ids=None, random_pbr=True,
                  shadows=True, render_chunk=None, plane_size=(3.0, 3.0), light_color=(300.0, 300.0, 300.0),
@@ -230,6 +250,7 @@ class SceneBatch:
                 self.env_ids = ids
                 self.d_env_ids = torch.from_numpy(ids.copy()).to(dev)
             self.d_env_out = torch.full((self.n_scenes, 3), -1, dtype=torch.int32, device=dev)
+        self.view, self.object_to_camera, self._view_keep = 0, None, None      # place(view=...)
 
     # ---- camera (shared by all scenes of the batch; sl.Scene's setters) --------------------------------------
     def _set_projection(self):
@@ -303,30 +324,72 @@ class SceneBatch:
         """What the list capacities cost the last settle() (slhip_settle_caps, SettleEngine.caps; synchronises the settle stream)."""
         return self.se.caps(self.n_scenes, self._settle_stream, self._settle_keep)
 
-    def place(self):
+    def _env(self):
+        d_ls, d_bg, d_pt = self.environment.device()
+        e = _abi.SynthEnv()
+        e.d_light_sets, e.d_backgrounds, e.d_plane_textures = d_ls.data_ptr(), d_bg.data_ptr(), d_pt.data_ptr()
+        e.d_env_ids = self.d_env_ids.data_ptr() if self.d_env_ids is not None else None
+        e.n_light_sets, e.n_backgrounds, e.n_plane_textures = self.environment.counts()
+        e.p_light_map, e.p_background, e.p_plane_texture = self.env_probs
+        return e
+
+    def place(self, view=0, camera_poses=None, object_to_camera=False):
         """Camera pose, light direction, shadow matrix and the render records of every scene; with an environment bank also
-        every scene's light map / background image / plane texture and the shadow matrices of all its lights."""
+        every scene's light map / background image / plane texture and the shadow matrices of all its lights.
+
+        A view is another camera on the SAME physical scene: poses, world-space lights, environment and every draw / chunk
+        record keep their bits, only the camera and what hangs on it (world_to_cam, cam_position, the shadow matrices,
+        camera_pose of the scene records) are the view's.  `view` = 0 is the batch's camera; `view` = v >= 1 draws azimuth
+        and elevation as view 0 does, from the Philox key of view v (include/slhip.h, "Randomness"), and fits the camera to
+        the pile the same way.  `camera_poses`: a float32 device tensor [n_scenes, 4, 4] of camera-to-world matrices taken
+        as they are (no draw, no fit; `view` only names them); a pose with a non-finite entry leaves that scene empty.
+        `object_to_camera`: also keep world_to_cam * pose of every object, float32 [n_scenes, n_objects, 3, 4], in
+        `batch.object_to_camera` (sl.bop.scene_gt_entries).  The records are overwritten in place: a view costs no memory."""
+        check_view_arguments(view, camera_poses, self.n_scenes, self.eng.device)
         d_assets, d_templates = self.table.device()
         stream = torch.cuda.current_stream(self.eng.device).cuda_stream
-        if self.environment is not None:
-            d_ls, d_bg, d_pt = self.environment.device()
-            e = _abi.SynthEnv()
-            e.d_light_sets, e.d_backgrounds, e.d_plane_textures = d_ls.data_ptr(), d_bg.data_ptr(), d_pt.data_ptr()
-            e.d_env_ids = self.d_env_ids.data_ptr() if self.d_env_ids is not None else None
-            e.n_light_sets, e.n_backgrounds, e.n_plane_textures = self.environment.counts()
-            e.p_light_map, e.p_background, e.p_plane_texture = self.env_probs
+        if view != 0 or camera_poses is not None or object_to_camera:
+            v = _abi.SynthView()
+            v.view = int(view)
+            v.d_camera_poses = camera_poses.data_ptr() if camera_poses is not None else None
+            if object_to_camera:
+                if self.object_to_camera is None:
+                    self.object_to_camera = torch.empty((self.n_scenes, self.n_objects, 3, 4), dtype=torch.float32,
+                                                        device=self.eng.device)
+                v.d_object_to_camera = self.object_to_camera.data_ptr()
+            e = self._env() if self.environment is not None else None
+            with torch.cuda.device(self.eng.device):
+                st = self.eng.L.slhip_synth_place_view(self._p(), C.byref(e) if e is not None else None, C.byref(v),
+                                                       self._a(d_assets), self._a(d_templates), self._a(self.d_bodies),
+                                                       self._a(self.d_objects), self._a(self.d_scenes), self._a(self.d_srec),
+                                                       self._a(self.d_drec), self._a(self.d_crec), self._a(self.d_env_out),
+                                                       C.c_void_p(stream))
+            _abi.check(st, "slhip_synth_place_view")
+            self._view_keep = camera_poses          # alive until the next place(): the launch reads it on the stream
+        elif self.environment is not None:
+            e = self._env()
             with torch.cuda.device(self.eng.device):
                 st = self.eng.L.slhip_synth_place_env(self._p(), C.byref(e), self._a(d_assets), self._a(d_templates),
                                                       self._a(self.d_bodies), self._a(self.d_objects), self._a(self.d_scenes),
                                                       self._a(self.d_srec), self._a(self.d_drec), self._a(self.d_crec),
                                                       self._a(self.d_env_out), C.c_void_p(stream))
             _abi.check(st, "slhip_synth_place_env")
-            return
-        with torch.cuda.device(self.eng.device):
-            st = self.eng.L.slhip_synth_place(self._p(), self._a(d_assets), self._a(d_templates), self._a(self.d_bodies),
-                                              self._a(self.d_objects), self._a(self.d_scenes), self._a(self.d_srec),
-                                              self._a(self.d_drec), self._a(self.d_crec), C.c_void_p(stream))
-        _abi.check(st, "slhip_synth_place")
+        else:
+            with torch.cuda.device(self.eng.device):
+                st = self.eng.L.slhip_synth_place(self._p(), self._a(d_assets), self._a(d_templates), self._a(self.d_bodies),
+                                                  self._a(self.d_objects), self._a(self.d_scenes), self._a(self.d_srec),
+                                                  self._a(self.d_drec), self._a(self.d_crec), C.c_void_p(stream))
+            _abi.check(st, "slhip_synth_place")
+        self.view = int(view)
+
+    def views(self, n, mask=_abi.OUT_GT6, ssao=True, object_stats=False, object_to_camera=False):
+        """n pictures of every scene: places view v = 0 .. n - 1 in turn and yields (v, chunk, buffers) for every render chunk
+        of it, view-major.  The records of a view are gone once the next one is placed: read what is needed of them
+        (host_cameras(), object_to_camera) while the view's items are being consumed."""
+        for v in range(int(n)):
+            self.place(view=v, object_to_camera=object_to_camera)
+            for c in range(self.n_render_chunks()):
+                yield v, c, self.render(c, mask, ssao, object_stats=object_stats)
 
     @property
     def render_chunk(self):
@@ -381,6 +444,10 @@ class SceneBatch:
                 self._host(self.d_drec, _abi.DRAW_DTYPE, self.n_scenes * md),
                 self._host(self.d_crec, _abi.CHUNK_DTYPE, self.n_scenes * mk))
 
+    def host_cameras(self):
+        """[n_scenes, 4, 4] float32: camera-to-world of every scene in the view last placed (Scene.camera_pose)."""
+        return self.host_scenes()["camera_pose"].reshape(self.n_scenes, 4, 4).copy()
+
     def host_env(self):
         """[n_scenes, 3] int32: the (light set, background, plane texture) of the bank every scene got at place(); -1 = none."""
         if self.environment is None:
@@ -390,7 +457,8 @@ class SceneBatch:
     def scene(self, index, _cache=None):
         """Scene `index` as an ordinary sl.Scene (objects, poses, velocities, camera, light, plane, and the light map /
         background image / plane texture it got from the environment bank) rebuilt from the device records -- the hand-over
-        to the per-scene API (serialize, render with other settings, ...)."""
+        to the per-scene API (serialize, render with other settings, ...).  The camera is read from the records, so the scene
+        is handed over with the camera of the view last placed (`batch.view`)."""
         from .object import Object
         from .scene import Scene
 

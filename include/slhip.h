@@ -43,7 +43,8 @@ extern "C" {
                                     stabilisation state of a body, SLHIP_BODY_FROZEN; slhip_settle_solver_wave_lds, slhip_host_convex_hull,
                                     slhip_host_fill_holes
                                  5, additive (no struct or signature changed; detect with dlsym): slhip_object_stats,
-                                    slhip_render_object_stats, slhip_render_object_stats_bytes                                 */
+                                    slhip_render_object_stats, slhip_render_object_stats_bytes; slhip_object_mask,
+                                    slhip_render_object_masks, slhip_render_object_masks_bytes, slhip_object_masks_expand       */
 #define SLHIP_NUM_LIGHTS 3 /* reference include/stillleben/common.h:17 */
 
 /* ---------------------------------------------------------------------------------------------
@@ -320,6 +321,59 @@ int slhip_render_object_stats(const slhip_mesh_pool* pool,
                               uint32_t width, uint32_t height, const slhip_render_scratch* scratch,
                               uint32_t n_slots, uint64_t* d_words, uint64_t capacity_words,
                               slhip_object_stats* d_out, uint64_t* words_needed, void* stream);
+
+/* Per-object masks of a render (slhip_render_object_masks): of every (scene, slot) the whole silhouette (kind 0: the pixels
+ * px_all counts, BOP's mask/) and the visible part (kind 1: the pixels px_visib counts, BOP's mask_visib/), in two forms --
+ *   bit tiles: one u64 word per 8 x 8-pixel tile of the slot's tile box (the box of slhip_render_object_stats' working pool),
+ *              for slhip_object_masks_expand or a kernel of the caller's;
+ *   run lengths: the uncompressed RLE of COCO / the BOP toolkit's scene_gt_coco.json, {"counts": [...], "size": [H, W]}:
+ *              the mask read column by column (pixel (x, y) at position x * H + y), lengths of zeros and ones in turn, zeros
+ *              first (a first length of 0 when pixel (0, 0) is set), summing to W * H; an empty mask is the single length W * H.
+ * Record per (scene, slot), device, [n_scenes][n_slots].  56 bytes.  A slot whose whole silhouette is empty (unused, outside
+ * the picture, behind the camera) has no tiles. */
+typedef struct {
+    int32_t  tile_box[4];     /* tx0, ty0, tx1, ty1 in 8x8 tiles; tx0 > tx1: the slot has no tiles            */
+    uint64_t word_offset[2];  /* first u64 word of kind 0 (whole silhouette) and 1 (visible) in d_words;
+                                 row-major over the tile box, bit (y & 7) * 8 + (x & 7) = pixel (x, y)         */
+    uint64_t rle_offset[2];   /* first u32 run length of each kind in d_runs                                   */
+    uint32_t rle_count[2];    /* number of run lengths of each kind                                           */
+} slhip_object_mask;
+
+#define SLHIP_OBJECT_MASKS_CAPACITY 2   /* status of slhip_render_object_masks: the word pool or the run pool is too small */
+
+/* Worst-case sizes of the two pools of slhip_render_object_masks.  Words: both kinds of every slot 1..n_slots-1 over the whole
+ * viewport, twice slhip_render_object_stats_bytes.  Run lengths: W * H + 1 per mask of a slot 1..n_slots-1 (a mask that
+ * changes at every pixel) and 1 per mask of slot 0.  Real use is FAR below both: words follow the objects' screen boxes, and
+ * a mask of a convex shape has about two run lengths per image column it covers -- start from a modest size and let the
+ * capacity status grow the pools rather than allocating these.  Host only.                                                  */
+int slhip_render_object_masks_bytes(uint32_t n_scenes, uint32_t n_slots, uint32_t width, uint32_t height,
+                                    uint64_t* worst_words, uint64_t* worst_runs);
+
+/* slhip_render_object_stats plus the masks: the same arguments, precondition and statistics (d_out is filled bit for bit as
+ * by that call), and
+ *   d_words   holds both kinds, so it needs twice the words the statistics call reports; the words stay valid after the call
+ *   d_masks   slhip_object_mask [n_scenes][n_slots] (device)
+ *   d_runs    u32 pool of capacity_runs run lengths (device)
+ *   words_needed, runs_needed  (host, may be NULL) what this batch needs, as far as the call got to know it
+ * Returns 0, SLHIP_OBJECT_MASKS_CAPACITY when either pool is too small (no partial result is promised; grow the pools and call
+ * again -- the render's outputs stay valid), or a negative error (slhip_last_error).  width * height must be below 2^31.
+ * Synchronises `stream` twice: after the tile scan and after the run count.                                                 */
+int slhip_render_object_masks(const slhip_mesh_pool* pool,
+                              const slhip_scene* d_scenes, const slhip_draw* d_draws,
+                              const slhip_chunk* d_chunks, uint32_t n_scenes, uint32_t n_draws, uint32_t n_chunks,
+                              uint32_t width, uint32_t height, const slhip_render_scratch* scratch,
+                              uint32_t n_slots, uint64_t* d_words, uint64_t capacity_words,
+                              slhip_object_stats* d_out, uint64_t* words_needed,
+                              slhip_object_mask* d_masks, uint32_t* d_runs, uint64_t capacity_runs, uint64_t* runs_needed,
+                              void* stream);
+
+/* Bit tiles to dense masks.  d_select holds n_select pairs (scene, slot) as u32 (device); d_dense is uint8
+ * [n_select][height][width] with values 0 / 1 (device).  Every byte is written: pixels outside the slot's tile box, of an empty
+ * slot or of a pair outside [n_scenes][n_slots] are 0.  kind: 0 the whole silhouette, 1 the visible part.  Returns 0 or a
+ * negative error (null pointers, zero sizes and kind > 1 are rejected before anything touches the device).                  */
+int slhip_object_masks_expand(const slhip_object_mask* d_masks, const uint64_t* d_words, uint32_t n_scenes, uint32_t n_slots,
+                              uint32_t width, uint32_t height, uint32_t kind, const uint32_t* d_select, uint64_t n_select,
+                              uint8_t* d_dense, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Settle half (replaces PhysX as driven by Scene::simulateTableTopScene, scene.cpp:612-759)

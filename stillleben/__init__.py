@@ -11,6 +11,7 @@ from .lib.libstillleben_python import _set_install_prefix  # noqa: F401
 from stillleben_amd import AssetTable, SceneBatch  # noqa: F401  (additive: the batch dimension of the GPU path)
 from stillleben_amd import EnvironmentBank  # noqa: F401  (additive: the environment bank of a SceneBatch)
 from stillleben_amd import ObjectStats  # noqa: F401  (additive: per-object visibility statistics)
+from stillleben_amd import ObjectMasks  # noqa: F401  (additive: per-object masks as bit tiles and COCO run lengths)
 from stillleben_amd import bop  # noqa: F401  (additive: BOP entries of a SceneBatch's views)
 
 __all__ = _impl.__all__

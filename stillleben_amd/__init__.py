@@ -22,6 +22,7 @@ from .job_queue import JobQueue  # noqa: F401
 from .scene_batch import AssetTable, SceneBatch  # noqa: F401  (additive: the batch dimension of the GPU path)
 from .environment import EnvironmentBank  # noqa: F401  (additive: light maps / backgrounds / plane textures of a SceneBatch)
 from .object_stats import ObjectStats  # noqa: F401  (additive: per-object visibility statistics, BOP's scene_gt_info)
+from .object_masks import ObjectMasks  # noqa: F401  (additive: per-object masks, BOP's mask/, mask_visib/ and scene_gt_coco)
 from . import camera_model, diff, losses, extension, profiling  # noqa: F401
 from . import bop  # noqa: F401  (additive: BOP scene_camera / scene_gt entries from a SceneBatch's records)
 
@@ -29,7 +30,7 @@ __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
     'Mesh', 'MeshCache', 'Object', 'Range3D', 'RenderPass', 'RenderPassResult', 'Scene', 'Texture',
     'Texture2D', 'Viewer', 'view', 'ManipulationSim', 'JobQueue', 'AssetTable', 'SceneBatch',
-    'camera_model', 'diff', 'extension', 'losses', 'quat_to_matrix', 'matrix_to_quat', 'ObjectStats', 'EnvironmentBank',
+    'camera_model', 'diff', 'extension', 'losses', 'quat_to_matrix', 'matrix_to_quat', 'ObjectStats', 'ObjectMasks', 'EnvironmentBank',
     'bop',
 ]
 

@@ -40,6 +40,7 @@ RENDER_SHADOWS = 0x200
 RENDER_SHADOW_RESET = 0x400
 RENDER_KEEP_HDR = 0x800
 OBJECT_STATS_CAPACITY = 1     # SLHIP_OBJECT_STATS_CAPACITY: status of slhip_render_object_stats when the word pool is too small
+OBJECT_MASKS_CAPACITY = 2     # SLHIP_OBJECT_MASKS_CAPACITY: status of slhip_render_object_masks when the word or the run pool is too small
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
 COMM_ID_BYTES = 128
@@ -145,6 +146,11 @@ CHUNK_DTYPE = np.dtype(
 OBJECT_STATS_DTYPE = np.dtype([("px_visib", np.uint32), ("px_all", np.uint32), ("bbox_visib", np.int32, (4,)),
                                ("bbox_obj", np.int32, (4,))])
 assert OBJECT_STATS_DTYPE.itemsize == 40, OBJECT_STATS_DTYPE.itemsize
+
+# slhip_object_mask (include/slhip.h): per (scene, slot) layout of the bit tiles and run lengths of both mask kinds, 56 bytes
+OBJECT_MASK_DTYPE = np.dtype([("tile_box", np.int32, (4,)), ("word_offset", np.uint64, (2,)), ("rle_offset", np.uint64, (2,)),
+                              ("rle_count", np.uint32, (2,))])
+assert OBJECT_MASK_DTYPE.itemsize == 56, OBJECT_MASK_DTYPE.itemsize
 
 # slhip_host_object / slhip_host_scene (include/slhip.h): flat descriptors for the C++ record assembly
 HOST_OBJECT_DTYPE = np.dtype([
@@ -333,6 +339,15 @@ def lib():
         C.POINTER(RenderScratch), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p,
     ]
     L.slhip_render_object_stats_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.slhip_render_object_masks.argtypes = [
+        C.POINTER(MeshPool), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+        C.POINTER(RenderScratch), C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64),
+        C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
+    ]
+    L.slhip_render_object_masks_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint64)]
+    L.slhip_object_masks_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.slhip_render_ssao_skipped.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64 * 2), C.c_void_p]
     L.slhip_settle_caps.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64 * 10), C.c_void_p]
     L.slhip_settle_timing_enable.argtypes = [C.c_int]

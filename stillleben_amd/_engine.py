@@ -34,6 +34,7 @@ class RenderBuffers:
         self.bary = mk(_abi.OUT_BARY, (B, H, W, 4), torch.float32)
         self.cam_coord = mk(_abi.OUT_CAM_COORD, (B, H, W, 4), torch.float32)
         self.object_stats = None   # ObjectStats of the last render into these buffers, when it was asked for
+        self.object_masks = None   # ObjectMasks of the last render into these buffers, when they were asked for
 
     def abi(self):
         o = _abi.RenderOut()
@@ -141,29 +142,31 @@ class Engine:
         return torch.from_numpy(raw.copy()).to(self.device)
 
     def render(self, scenes, mask=_abi.OUT_ALL, ssao=True, shadows=True, depth_peel=None, predicate=None,
-               buffers=None, keep_hdr=False, object_stats=False):
+               buffers=None, keep_hdr=False, object_stats=False, object_masks=False):
         """`object_stats`: also compute the per-object visibility statistics (buffers.object_stats, an ObjectStats with one
         slot per instance index up to the largest of the batch's objects -- filtered out by `predicate` or not).  Not with
-        `depth_peel`: a peeled layer has no single "whole silhouette" (ValueError)."""
+        `depth_peel`: a peeled layer has no single "whole silhouette" (ValueError).  `object_masks`: the statistics and the
+        per-object masks (buffers.object_masks, an ObjectMasks), under the same rules."""
         W, H = scenes[0]._viewport
         for s in scenes:
             if s._viewport != (W, H):
                 raise ValueError("all scenes of a batch must share one viewport")
-        if object_stats and depth_peel is not None:
-            raise ValueError("object_stats cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
+        if (object_stats or object_masks) and depth_peel is not None:
+            raise ValueError("object_stats / object_masks cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
         n_slots = None
-        if object_stats:
+        if object_stats or object_masks:
             n_slots = 1 + max((int(o.instance_index) for s in scenes for o in s._objects), default=0)
         want_rgb = bool(mask & _abi.OUT_RGB)
         srec, drec, crec = build_batch(scenes, self.pool, predicate, with_shadows=shadows and want_rgb)
         return self.render_records(srec, drec, crec, W, H, mask, ssao, shadows, depth_peel, buffers, keep_hdr,
-                                   object_stats=object_stats, n_slots=n_slots)
+                                   object_stats=object_stats, n_slots=n_slots, object_masks=object_masks)
 
     def render_records(self, srec, drec, crec, W, H, mask=_abi.OUT_ALL, ssao=True, shadows=True, depth_peel=None,
-                       buffers=None, keep_hdr=False, object_stats=False, n_slots=None, stats_capacity=None):
+                       buffers=None, keep_hdr=False, object_stats=False, n_slots=None, stats_capacity=None,
+                       object_masks=False, masks_capacity=None):
         """Renders a batch described by prebuilt slhip_scene / slhip_draw / slhip_chunk records (host arrays).  With
-        `object_stats` and no `n_slots`: one slot per instance index up to the largest of the draws."""
-        if object_stats and n_slots is None:
+        `object_stats` or `object_masks` and no `n_slots`: one slot per instance index up to the largest of the draws."""
+        if (object_stats or object_masks) and n_slots is None:
             n_slots = 1 + (int((drec["instance_index"] & 0xFFFF).max()) if len(drec) else 0)
         d_s, d_d, d_c = self.upload_records(srec), self.upload_records(drec), self.upload_records(crec)
         n_clip = int(drec["n_verts"].sum()) if len(drec) else 0
@@ -172,23 +175,26 @@ class Engine:
         lights = max(1, int(np.max(np.nonzero(on.any(axis=0))[0]) + 1)) if on.any() else 1
         buffers = self.render_device(d_s, d_d, d_c, len(srec), len(drec), len(crec), n_clip, W, H, mask, ssao, shadows,
                                      depth_peel, buffers, keep_hdr, shadow_lights=lights, object_stats=object_stats,
-                                     n_slots=n_slots, stats_capacity=stats_capacity)
+                                     n_slots=n_slots, stats_capacity=stats_capacity, object_masks=object_masks,
+                                     masks_capacity=masks_capacity)
         buffers._keepalive += (d_s, d_d, d_c)   # alive until the stream has consumed them
         return buffers
 
     def render_device(self, d_s, d_d, d_c, B, n_draws, n_chunks, n_clip, W, H, mask=_abi.OUT_ALL, ssao=True, shadows=True,
                       depth_peel=None, buffers=None, keep_hdr=False, shadow_lights=_abi.NUM_LIGHTS, object_stats=False,
-                      n_slots=None, stats_capacity=None):
+                      n_slots=None, stats_capacity=None, object_masks=False, masks_capacity=None):
         """slhip_render on records that already live in HBM (device tensors or raw device addresses):
         `n_clip` = clip-position slots the draws' clip_base + n_verts ranges span; `shadow_lights` = shadow maps per scene
         (lights with a higher index cast no shadow).  `object_stats`: slhip_render_object_stats right after the render on the
         same stream, with `n_slots` slots per scene (required) -> buffers.object_stats; not with `depth_peel` (ValueError).
-        `stats_capacity`: words of the stats pool to start from (tests; the pool grows as needed)."""
-        if object_stats:
+        `stats_capacity`: words of the stats pool to start from (tests; the pool grows as needed).  `object_masks`:
+        slhip_render_object_masks in place of the statistics call -> buffers.object_stats and buffers.object_masks, under the
+        same rules; `masks_capacity` = (words, run lengths) of its two pools to start from (tests)."""
+        if object_stats or object_masks:
             if depth_peel is not None:
-                raise ValueError("object_stats cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
+                raise ValueError("object_stats / object_masks cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
             if n_slots is None or int(n_slots) < 1:
-                raise ValueError("object_stats needs n_slots (the largest instance index of the batch + 1)")
+                raise ValueError("object_stats / object_masks need n_slots (the largest instance index of the batch + 1)")
         want_rgb = bool(mask & _abi.OUT_RGB)
         ssao = ssao and want_rgb
         shadows = shadows and want_rgb
@@ -228,7 +234,12 @@ class Engine:
         keep["shadow_ready"] = bool(shadows)
         buffers._keepalive = (keep,)
         buffers.object_stats = None
-        if object_stats:
+        buffers.object_masks = None
+        if object_masks:
+            buffers.object_masks = self._object_masks(pool, addr(d_s), addr(d_d), addr(d_c), B, n_draws, n_chunks, W, H, scratch,
+                                                      int(n_slots), stream, masks_capacity)
+            buffers.object_stats = buffers.object_masks.stats
+        elif object_stats:
             buffers.object_stats = self._object_stats(pool, addr(d_s), addr(d_d), addr(d_c), B, n_draws, n_chunks, W, H, scratch,
                                                       int(n_slots), stream, stats_capacity)
         return buffers
@@ -258,3 +269,39 @@ class Engine:
                                                     device=self.device)
         _abi.check(st, "slhip_render_object_stats")
         return ObjectStats.from_records(out)
+
+    def _object_masks(self, pool, d_s, d_d, d_c, B, n_draws, n_chunks, W, H, scratch, n_slots, stream, capacity=None):
+        """slhip_render_object_masks on the render just enqueued (same records, same scratch, same stream).  The word and run
+        pools start small (`capacity` = (words, run lengths), tests) and grow to what the call reports; only the masks call is
+        repeated.  The pools belong to the returned ObjectMasks: a later render does not overwrite them."""
+        from .object_masks import ObjectMasks
+        from .object_stats import ObjectStats
+
+        out = torch.empty((B, n_slots, 10), dtype=torch.int32, device=self.device)
+        rec = torch.empty((B, n_slots, 14), dtype=torch.int32, device=self.device)
+        sizes = self.__dict__.setdefault("_masks_sizes", {})     # what the last call on this stream needed: the next one's start
+        if capacity is not None:
+            n_words, n_runs = (max(int(v), 1) for v in capacity)
+        else:
+            n_words, n_runs = sizes.get(stream, (max(1 << 17, B * max(n_slots - 1, 1) * 512), max(1 << 16, B * n_slots * 512)))
+        words = torch.empty(n_words, dtype=torch.int64, device=self.device)
+        runs = torch.empty(n_runs, dtype=torch.int32, device=self.device)
+        need_w, need_r = C.c_uint64(0), C.c_uint64(0)
+        self.last_masks_calls = []      # (status, capacity_words, words_needed, capacity_runs, runs_needed) of each call
+        with torch.cuda.device(self.device):
+            for _ in range(4):
+                st = self.L.slhip_render_object_masks(C.byref(pool), d_s, d_d, d_c, B, n_draws, n_chunks, W, H, C.byref(scratch),
+                                                      n_slots, _ptr(words), words.numel(), _ptr(out), C.byref(need_w),
+                                                      _ptr(rec), _ptr(runs), runs.numel(), C.byref(need_r), C.c_void_p(stream))
+                nw, nr = int(need_w.value), int(need_r.value)
+                self.last_masks_calls.append((st, words.numel(), nw, runs.numel(), nr))
+                if st != _abi.OBJECT_MASKS_CAPACITY:
+                    break
+                if nw > words.numel():
+                    words = torch.empty(nw + nw // 4 + 1024, dtype=torch.int64, device=self.device)
+                if nr > runs.numel():
+                    runs = torch.empty(nr + nr // 4 + 1024, dtype=torch.int32, device=self.device)
+        _abi.check(st, "slhip_render_object_masks")
+        if capacity is None:
+            sizes[stream] = (words.numel(), runs.numel())
+        return ObjectMasks(ObjectStats.from_records(out), rec, words, runs, (H, W))

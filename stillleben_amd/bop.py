@@ -7,6 +7,8 @@ A BOP scene is one physical scene with many images: `scene_camera.json` and `sce
     cams, o2c = batch.host_cameras(), batch.object_to_camera.cpu().numpy()
     scene_camera[str(v)] = sl.bop.scene_camera_entry((fx, fy, cx, cy), cams[b])
     scene_gt[str(v)] = sl.bop.scene_gt_entries(o2c[b], mesh_to_object, class_indices)
+    masks = batch.render(c, object_masks=True).object_masks          # sl.ObjectMasks: mask/ and mask_visib/ of the chunk
+    coco["annotations"] += sl.bop.scene_gt_coco_annotations(masks, b, class_indices, image_id=v, first_id=len(coco["annotations"]) + 1)
 
 The camera frame of the renderer is OpenCV's already (x right, y down, z into the picture: the rotation C of
 scene.cpp:489-493 maps camera x, y, z to world -y, -z, +x), so no axis is flipped.  Lengths are metres in the records and
@@ -78,3 +80,23 @@ def scene_gt_entries(object_to_camera, mesh_to_object, class_indices):
                     "cam_t_m2c": [float(v) for v in m2c[:, 3] * MM],
                     "obj_id": ids[i]})
     return out
+
+
+def scene_gt_coco_annotations(masks, b, class_indices, image_id, first_id=1):
+    """One image's annotations of scene_gt_coco.json from an sl.ObjectMasks: one dict per slot 1..S-1 of scene b, in slot order,
+    with the keys the BOP toolkit writes -- id (first_id, first_id + 1, ...), image_id, category_id (class_indices[i - 1]),
+    iscrowd (always 0), area (= px_count_visib), bbox (= bbox_visib, (x, y, w, h)), segmentation (the VISIBLE mask as
+    uncompressed RLE, {"counts", "size": [H, W]}), width, height -- and one key more, `segmentation_all`: the amodal RLE (the
+    whole silhouette).  That key is this project's addition; COCO readers ignore it.  Slots that show nothing are listed as
+    well (area 0, bbox -1s, segmentation [H * W]), as ObjectStats.to_bop lists them."""
+    ids = [int(v) for v in class_indices]
+    if len(ids) != masks.n_slots - 1:
+        raise ValueError("class_indices: one per object slot 1..S-1")
+    one = masks if masks._single else masks[b]
+    visib, whole = one.rles("visib"), one.rles("all")
+    area = one.stats.px_count_visib.detach().cpu().tolist()
+    bbox = one.stats.bbox_visib.detach().cpu().tolist()
+    H, W = masks.size
+    return [{"id": int(first_id) + i - 1, "image_id": int(image_id), "category_id": ids[i - 1], "iscrowd": 0,
+             "area": int(area[i]), "bbox": [int(v) for v in bbox[i]], "segmentation": visib[i - 1],
+             "segmentation_all": whole[i - 1], "width": W, "height": H} for i in range(1, masks.n_slots)]

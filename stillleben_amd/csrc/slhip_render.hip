@@ -2588,3 +2588,4 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
 
 // per-object visibility statistics (slhip_render_object_stats): kernels that reuse the raster core above
 #include "slhip_render_stats.inc"
+#include "slhip_render_masks.inc"

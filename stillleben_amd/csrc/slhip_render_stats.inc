@@ -532,26 +532,32 @@ extern "C" int slhip_render_object_stats_bytes(uint32_t n_scenes, uint32_t n_slo
     return 0;
 }
 
-extern "C" int slhip_render_object_stats(const slhip_mesh_pool* pool, const slhip_scene* d_scenes, const slhip_draw* d_draws,
-                                         const slhip_chunk* d_chunks, uint32_t n_scenes, uint32_t n_draws, uint32_t n_chunks,
-                                         uint32_t width, uint32_t height, const slhip_render_scratch* scratch, uint32_t n_slots,
-                                         uint64_t* d_words, uint64_t capacity_words, slhip_object_stats* d_out,
-                                         uint64_t* words_needed, void* stream_)
+namespace {
+
+// the layout hook of slhip_render_object_masks (slhip_render_masks.inc): keeps every slot's tile box and word offset before
+// k_os_silhouette overwrites them
+void om_save_layout(slhip_object_mask* d_masks, const OsRec* out, size_t n, unsigned long long total, hipStream_t stream);
+
+// The body shared by slhip_render_object_stats and slhip_render_object_masks (`who` names the entry in error texts).  `kinds`
+// word runs of the scanned size follow one another in the pool (1: the silhouettes; 2: the visible bits after them, all zero
+// on return); `d_masks` (masks entry only) receives the layout; `capacity_status` is the entry's "pool too small" status.
+int os_run(const char* who, int capacity_status, const slhip_mesh_pool* pool, const slhip_scene* d_scenes, const slhip_draw* d_draws,
+           const slhip_chunk* d_chunks, uint32_t n_scenes, uint32_t n_chunks, uint32_t width, uint32_t height,
+           const slhip_render_scratch* scratch, uint32_t n_slots, uint64_t* d_words, uint64_t capacity_words, unsigned kinds,
+           slhip_object_stats* d_out, slhip_object_mask* d_masks, uint64_t* words_needed, hipStream_t stream)
 {
-    (void)n_draws;
-    hipStream_t stream = (hipStream_t)stream_;
     if (!pool || !d_scenes || !d_draws || !scratch || !d_words || !d_out) {
-        slhip::set_error("slhip_render_object_stats: null argument (mesh pool, scenes, draws, scratch, word pool and output are required)");
+        slhip::set_error("%s: null argument (mesh pool, scenes, draws, scratch, word pool and output are required)", who);
         return -1;
     }
     if (n_chunks > 0 && !d_chunks) {
-        slhip::set_error("slhip_render_object_stats: null chunk list");
+        slhip::set_error("%s: null chunk list", who);
         return -1;
     }
     if (words_needed) *words_needed = 0;
     if (n_scenes == 0 || n_slots == 0 || width == 0 || height == 0) return 0;
     if (!scratch->d_vis || !scratch->d_queue || (n_chunks > 0 && (!scratch->d_clip || !scratch->d_vattr || scratch->n_clip_verts == 0))) {
-        slhip::set_error("slhip_render_object_stats: the render's d_vis, d_queue, d_clip and d_vattr scratch are required");
+        slhip::set_error("%s: the render's d_vis, d_queue, d_clip and d_vattr scratch are required", who);
         return -1;
     }
     const int W = (int)width, H = (int)height;
@@ -574,14 +580,15 @@ extern "C" int slhip_render_object_stats(const slhip_mesh_pool* pool, const slhi
     unsigned long long total = 0;
     SLHIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, stream));
     SLHIP_CHECK(hipStreamSynchronize(stream));
-    if (words_needed) *words_needed = total;
-    if (total > capacity_words) {
-        slhip::set_error("slhip_render_object_stats: the word pool holds %llu words, this batch needs %llu",
-                         (unsigned long long)capacity_words, total);
-        return SLHIP_OBJECT_STATS_CAPACITY;
+    if (words_needed) *words_needed = total * kinds;
+    if (total * kinds > capacity_words) {
+        slhip::set_error("%s: the word pool holds %llu words, this batch needs %llu", who,
+                         (unsigned long long)capacity_words, total * kinds);
+        return capacity_status;
     }
-    if (total > 0) SLHIP_CHECK(hipMemsetAsync(words, 0, (size_t)total * 8, stream));
+    if (total > 0) SLHIP_CHECK(hipMemsetAsync(words, 0, (size_t)total * kinds * 8, stream));
     SLHIP_CHECK(hipMemsetAsync(scratch->d_queue, 0, 16, stream));
+    if (d_masks) om_save_layout(d_masks, out, n, total, stream);
     if (n_chunks > 0 && total > 0) {
         k_os_raster<false><<<n_chunks, 256, 0, stream>>>(*pool, d_draws, d_chunks, n_chunks, W, H, out, n_slots, words,
                                                          scratch->d_queue, scratch->queue_capacity, clipbuf, screen);
@@ -598,4 +605,17 @@ extern "C" int slhip_render_object_stats(const slhip_mesh_pool* pool, const slhi
     k_os_finish<<<gs, 256, 0, stream>>>(out, n);
     SLHIP_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int slhip_render_object_stats(const slhip_mesh_pool* pool, const slhip_scene* d_scenes, const slhip_draw* d_draws,
+                                         const slhip_chunk* d_chunks, uint32_t n_scenes, uint32_t n_draws, uint32_t n_chunks,
+                                         uint32_t width, uint32_t height, const slhip_render_scratch* scratch, uint32_t n_slots,
+                                         uint64_t* d_words, uint64_t capacity_words, slhip_object_stats* d_out,
+                                         uint64_t* words_needed, void* stream_)
+{
+    (void)n_draws;
+    return os_run("slhip_render_object_stats", SLHIP_OBJECT_STATS_CAPACITY, pool, d_scenes, d_draws, d_chunks, n_scenes, n_chunks,
+                  width, height, scratch, n_slots, d_words, capacity_words, 1u, d_out, nullptr, words_needed, (hipStream_t)stream_);
 }

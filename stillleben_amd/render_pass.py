@@ -67,6 +67,20 @@ class RenderPassResult:
         cuda = require_context().cuda_outputs
         return st[self._index].map(lambda t: t.clone() if cuda else t.cpu())
 
+    def object_masks(self):
+        """Per-object masks of the rendered scene (sl.ObjectMasks, the single scene's view: dense(kind, slots=...), rle(i, kind),
+        rles(kind); slot i = instance index i), computed when RenderPass.object_masks_enabled was set for the render.  Raises
+        RuntimeError otherwise.  The bit tiles and run lengths stay on the device; `.stats` follows the other accessors."""
+        if self._buffers is None:
+            raise RuntimeError("RenderPassResult is empty: render something first")
+        om = self._buffers.object_masks
+        if om is None:
+            raise RuntimeError("the last render did not compute object masks (set RenderPass.object_masks_enabled)")
+        cuda = require_context().cuda_outputs
+        one = om[self._index]
+        one.stats = one.stats.map(lambda t: t.clone() if cuda else t.cpu())
+        return one
+
 
 class RenderPass:
     def __init__(self, shading="pbr"):
@@ -76,20 +90,23 @@ class RenderPass:
         self._shading = shading  # stored, never read by the render path (quirk q2)
         self.ssao_enabled = True  # render_pass.h:150
         self.object_stats_enabled = False   # additive: per-object visibility statistics (RenderPassResult.object_stats())
+        self.object_masks_enabled = False   # additive: per-object masks (RenderPassResult.object_masks(); the statistics come along)
         self._result = RenderPassResult()
         self._buffers = None
 
     def render(self, scene, result=None, depth_peel=None, predicate=None):
-        """With object_stats_enabled, a `depth_peel` render raises ValueError: a peeled layer has no single whole silhouette."""
-        if self.object_stats_enabled and depth_peel is not None:
-            raise ValueError("object statistics cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
+        """With object_stats_enabled or object_masks_enabled, a `depth_peel` render raises ValueError: a peeled layer has no
+        single whole silhouette."""
+        if (self.object_stats_enabled or self.object_masks_enabled) and depth_peel is not None:
+            raise ValueError("object statistics / masks cannot be combined with depth_peel: a peeled layer has no single whole silhouette")
         res = result if result is not None else self._result
         peel = None
         if depth_peel is not None:
             peel = depth_peel._buffers.coord[depth_peel._index:depth_peel._index + 1].contiguous()
         own = res._buffers if (res._buffers is not None and res._buffers.B == 1 and res is not depth_peel) else None
         res._buffers = engine().render([scene], _abi.OUT_ALL, ssao=self.ssao_enabled, shadows=True,
-                                       depth_peel=peel, predicate=predicate, buffers=own, object_stats=self.object_stats_enabled)
+                                       depth_peel=peel, predicate=predicate, buffers=own, object_stats=self.object_stats_enabled,
+                                       object_masks=self.object_masks_enabled)
         res._index = 0
         return res
 

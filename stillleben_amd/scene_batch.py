@@ -382,14 +382,14 @@ class SceneBatch:
             _abi.check(st, "slhip_synth_place")
         self.view = int(view)
 
-    def views(self, n, mask=_abi.OUT_GT6, ssao=True, object_stats=False, object_to_camera=False):
+    def views(self, n, mask=_abi.OUT_GT6, ssao=True, object_stats=False, object_to_camera=False, object_masks=False):
         """n pictures of every scene: places view v = 0 .. n - 1 in turn and yields (v, chunk, buffers) for every render chunk
         of it, view-major.  The records of a view are gone once the next one is placed: read what is needed of them
         (host_cameras(), object_to_camera) while the view's items are being consumed."""
         for v in range(int(n)):
             self.place(view=v, object_to_camera=object_to_camera)
             for c in range(self.n_render_chunks()):
-                yield v, c, self.render(c, mask, ssao, object_stats=object_stats)
+                yield v, c, self.render(c, mask, ssao, object_stats=object_stats, object_masks=object_masks)
 
     @property
     def render_chunk(self):
@@ -398,9 +398,10 @@ class SceneBatch:
     def n_render_chunks(self):
         return (self.n_scenes + self.render_chunk - 1) // self.render_chunk
 
-    def render(self, chunk=0, mask=_abi.OUT_GT6, ssao=True, buffers=None, object_stats=False):
+    def render(self, chunk=0, mask=_abi.OUT_GT6, ssao=True, buffers=None, object_stats=False, object_masks=False):
         """slhip_render of render chunk `chunk` (scenes [chunk * render_chunk, ...)) on the current stream.  `object_stats`: also
-        the per-object visibility statistics (the returned buffers' .object_stats; slot i = object i - 1 of a scene)."""
+        the per-object visibility statistics (the returned buffers' .object_stats; slot i = object i - 1 of a scene).
+        `object_masks`: the statistics and the per-object masks (.object_masks, an ObjectMasks; the same slots)."""
         rc = self.render_chunk
         s0 = chunk * rc
         B = min(rc, self.n_scenes - s0)
@@ -416,11 +417,12 @@ class SceneBatch:
             B, B * md, B * mk, B * mv, W, H, mask, ssao=ssao, shadows=self.shadows, buffers=buffers,
             # the synthesised scenes have one light, or as many as the largest light set of the bank (k_synth_place)
             shadow_lights=1 if self.environment is None else max(1, self.environment.max_lights),
-            object_stats=object_stats, n_slots=self.n_objects + 1)   # instance index = object + 1 (k_synth_place)
+            object_stats=object_stats, n_slots=self.n_objects + 1,   # instance index = object + 1 (k_synth_place)
+            object_masks=object_masks)
 
-    def render_chunks(self, mask=_abi.OUT_GT6, ssao=True, object_stats=False):
+    def render_chunks(self, mask=_abi.OUT_GT6, ssao=True, object_stats=False, object_masks=False):
         for c in range(self.n_render_chunks()):
-            yield self.render(c, mask, ssao, object_stats=object_stats)
+            yield self.render(c, mask, ssao, object_stats=object_stats, object_masks=object_masks)
 
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):

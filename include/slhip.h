@@ -268,6 +268,18 @@ int slhip_render_timings(float* ms_out);
  * slhip_render on `scratch` (same n_scenes, width, height) returns counts[0] = tiles, counts[1] = tiles skipped; synchronises.  */
 int slhip_render_ssao_skipped(const slhip_render_scratch* scratch, uint32_t n_scenes, uint32_t width, uint32_t height,
                               uint64_t counts[2], void* stream);
+/* ... and sample by sample: a plane tile near an object still leaves out the taps whose sample vectors are too short to reach it.
+ * A tile has a LEVEL: 0 = no taps (the tiles counted as skipped above, which are clear at the full radius, and some more),
+ * j = only the samples with 1.001 |s_k| > rho_j run (compacted lists in ascending k, nested, so the occlusion sum keeps its
+ * bits), 5 = all 64.  slhip_render_ssao_level_tables returns the thresholds rho[5], the list lengths
+ * counts[6] and the lists taps[6 * 64] (list j at taps + 64 j), no GPU needed.  slhip_render_ssao_levels reads the last slhip_render
+ * on `scratch` (same n_scenes, width, height): counts[0..5] = tiles per level, counts[6] = the end-of-band runs of the tap
+ * kernel, counts[7] = those of them that held pixels of more than one level; synchronises.  Environment, read at every
+ * slhip_render: SLHIP_SSAO_DEBUG=2 runs every tile at the full list, =3 keeps the levels and counts the end-of-band runs (they
+ * are zero otherwise); SLHIP_SSAO_BAND_ROWS = rows per band of the tap kernel (a multiple of 16, default 16; placement only).  */
+int slhip_render_ssao_level_tables(float rho[5], uint32_t counts[6], uint8_t taps[384]);
+int slhip_render_ssao_levels(const slhip_render_scratch* scratch, uint32_t n_scenes, uint32_t width, uint32_t height,
+                             uint64_t counts[8], void* stream);
 
 /* Bytes of each scratch buffer for a batch (host helper, no GPU needed).  `hdr` is sized for TWO float4 planes per scene: plane 0
  * = the fragment shader's linear colour (always written when rgb is asked for), plane 1 = the same after ambient occlusion, the

@@ -349,6 +349,8 @@ def lib():
     L.slhip_object_masks_expand.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.slhip_render_ssao_skipped.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64 * 2), C.c_void_p]
+    L.slhip_render_ssao_levels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64 * 8), C.c_void_p]
+    L.slhip_render_ssao_level_tables.argtypes = [C.POINTER(C.c_float * 5), C.POINTER(C.c_uint32 * 6), C.POINTER(C.c_uint8 * 384)]
     L.slhip_settle_caps.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64 * 10), C.c_void_p]
     L.slhip_settle_timing_enable.argtypes = [C.c_int]
     L.slhip_settle_timings.argtypes = [C.POINTER(C.c_float * 5), C.POINTER(C.c_uint32 * 5)]

@@ -136,6 +136,18 @@ class Engine:
             _abi.check(self.L.slhip_render_ssao_skipped(C.byref(a), buffers.B, W, H, C.byref(out), C.c_void_p(stream)), "slhip_render_ssao_skipped")
         return int(out[0]), int(out[1])
 
+    def ssao_levels(self, buffers, W, H):
+        """(tiles per SSAO level 0..5, end-of-band runs, those with mixed levels) of the render that filled `buffers`
+        (slhip_render_ssao_levels; synchronises)."""
+        keep = buffers._keepalive[0]
+        a = _abi.RenderScratch()
+        a.d_ao = _ptr(keep["ao"])
+        out = (C.c_uint64 * 8)()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _abi.check(self.L.slhip_render_ssao_levels(C.byref(a), buffers.B, W, H, C.byref(out), C.c_void_p(stream)), "slhip_render_ssao_levels")
+        return [int(v) for v in out[:6]], int(out[6]), int(out[7])
+
     # ---- render ----------------------------------------------------------------------------
     def upload_records(self, arr):
         raw = np.frombuffer(arr.tobytes(), dtype=np.uint8) if arr.size else np.zeros(16, np.uint8)

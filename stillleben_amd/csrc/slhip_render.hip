@@ -19,6 +19,9 @@
 // All arithmetic that feeds integer outputs or depth follows rules R1..R7 of
 // oracle/render_ref.c; this file is compiled with -ffp-contract=off so that only the explicit
 // fmaf() calls fuse.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <vector>
 #include <type_traits>
 #include "slhip_common.h"
@@ -1920,9 +1923,12 @@ __device__ __forceinline__ float ssao_rcp(float x)
     return __uint_as_float((__float_as_uint(r) & 0x7fffffffu) | (__float_as_uint(x) & 0x80000000u));
 }
 
-// occlusion of one pixel with geometry (normal n4, camera position f4): ssao_shader.frag:20-56 as the oracle's ssao_pass spells it
+// occlusion of one pixel with geometry (normal n4, camera position f4): ssao_shader.frag:20-56 as the oracle's ssao_pass spells it.
+// `kern`, `n_taps`: the sample kernel, or one of its compacted level lists (k_ssao_mask) -- the taps left out add exactly 0.0f, the
+// others run in the same order, and the sum keeps its bits.  kAll: the whole kernel, a loop of constant length (k_ssao).
+template <bool kAll = false>
 __device__ __forceinline__ float ssao_pixel(const float* __restrict__ proj, const float* __restrict__ camS, int W, int H, int i, int j,
-                                            float4 n4, float4 f4, const float* __restrict__ kern)
+                                            float4 n4, float4 f4, const float* __restrict__ kern, int n_taps = 64)
 {
     float n[3] = {n4.x, n4.y, n4.z};
     normalize3(n);
@@ -1953,8 +1959,7 @@ __device__ __forceinline__ float ssao_pixel(const float* __restrict__ proj, cons
     const bool w_is_z = proj[12] == 0.0f && proj[13] == 0.0f && proj[14] == 1.0f && proj[15] == 0.0f;
     float occlusion = 0.0f;
     auto taps = [&](auto w_is_z_c) {
-#pragma unroll 4
-    for (int k = 0; k < 64; ++k) {
+    auto tap = [&](int k) {
         const float s0 = kern[3 * k], s1 = kern[3 * k + 1], s2 = kern[3 * k + 2];
         const float spz = fmaf(nR[2], s2, fmaf(btR[2], s1, fmaf(tgR[2], s0, frag[2])));
         const float o0 = fmaf(D0, s2, fmaf(C0, s1, fmaf(B0, s0, A[0])));
@@ -1973,6 +1978,18 @@ __device__ __forceinline__ float ssao_pixel(const float* __restrict__ proj, cons
             add = tt * tt * (3.0f - 2.0f * tt);
         }
         occlusion += add;
+    };
+    if constexpr (kAll) {
+#pragma unroll 4
+        for (int k = 0; k < 64; ++k) tap(k);
+    } else {
+        // four taps at a time (their fetches in flight together), then the rest of a list whose length is no multiple of 4
+        int k = 0;
+        for (; k + 4 <= n_taps; k += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) tap(k + u);
+        }
+        for (; k < n_taps; ++k) tap(k);
     }
     };
     if (w_is_z) taps(std::true_type{});   // scene-uniform: the whole wave takes one side
@@ -2000,7 +2017,7 @@ __global__ __launch_bounds__(256) SLHIP_SSAO_KERNEL void k_ssao(const slhip_scen
     const int i = (int)(pix % (unsigned)W), j = (int)(pix / (unsigned)W);
     const float4 n4 = reinterpret_cast<const float4*>(nrm)[gp];
     if (n4.x == 0.0f && n4.y == 0.0f && n4.z == 0.0f) { ao[gp] = 1.0f; return; }
-    ao[gp] = ssao_pixel(proj, camS, W, H, i, j, n4, reinterpret_cast<const float4*>(cam)[gp], kern);
+    ao[gp] = ssao_pixel<true>(proj, camS, W, H, i, j, n4, reinterpret_cast<const float4*>(cam)[gp], kern);
 }
 
 // ---- SSAO only where something can occlude ----------------------------------------------------------------------------------
@@ -2016,8 +2033,23 @@ __global__ __launch_bounds__(256) SLHIP_SSAO_KERNEL void k_ssao(const slhip_scen
 // the taps for the rest, compacted: a wave walks the pixels of ONE noise class (x & 3, y & 3) of a 16-row band in raster order
 // and queues those that need the loop, 64 at a time (the taps of a wave still move together).
 constexpr int kSsaoTile = 8;
+// ... and sample by sample: sample k lies radius * |s_k| from its pixel, so it projects within ceil(rho * reach / (zmin - radius)) + 2
+// pixels of the tile for every rho >= 1.001 |s_k| (the same bound with the sample's own length in the numerator), and the kernel's
+// vectors are short (max 0.81, mean 0.22 of the radius).  A plane tile whose box at rho_j is clear has LEVEL j: only the taps with
+// 1.001 |s_k| > rho_j can land on anything but the plane, the others add exactly 0.0f and are left out; the rest run in ascending k,
+// so the non-zero additions happen in the same order.  Level 0 (rho_0 >= 1.001 max |s|) runs nothing, the last level runs all 64.
+// The lists are nested (a pixel may always run a longer list than its own): compacted copies of the table, built on the host.
+// Byte per tile: the level in bits 1.., and bit 0 = clear at the full radius (or no geometry at all): there k_ssao_apply hands the
+// colour through instead of blurring ones.  Bit 0 keeps the full radius although level 0 needs less: the blur's mean of ones is
+// wt * rcp(wt), one ulp from 1 now and then, so handing through MORE tiles would move the float image by that ulp.
+constexpr int kSsaoLevels = 6;
+constexpr float kSsaoRho[kSsaoLevels - 1] = {0.81f, 0.6f, 0.45f, 0.3f, 0.2f};
+__constant__ float c_ssao_level_kernel[kSsaoLevels * 192];
+struct SsaoLevelCounts { int n[kSsaoLevels]; };
+
 __global__ __launch_bounds__(256) void k_ssao_mask(const slhip_scene* __restrict__ scenes, int W, int H,
-                                                  const float2* __restrict__ tiles, unsigned char* __restrict__ skip, int dbg)
+                                                  const float2* __restrict__ tiles, unsigned char* __restrict__ skip, int dbg,
+                                                  unsigned* __restrict__ drain_stats)
 {
     extern __shared__ int s_sat[];              // (TH + 1) x (TW + 1)
     const int TW = W / kSsaoTile, TH = H / kSsaoTile, SW = TW + 1;
@@ -2025,6 +2057,7 @@ __global__ __launch_bounds__(256) void k_ssao_mask(const slhip_scene* __restrict
     const float2* T = tiles + (size_t)scene * (TW * TH);
     unsigned char* S = skip + (size_t)scene * (TW * TH);
     const float* proj = scenes[scene].proj;
+    if (scene == 0 && threadIdx.x < 2) drain_stats[threadIdx.x] = 0u;      // (k_ssao_tiled counts its end-of-band runs there)
     // the rule is derived for a plain perspective projection (no skew, w = camera z): anything else runs every pixel
     const bool persp = proj[1] == 0.0f && proj[3] == 0.0f && proj[4] == 0.0f && proj[7] == 0.0f &&
                        proj[12] == 0.0f && proj[13] == 0.0f && proj[14] == 1.0f && proj[15] == 0.0f && proj[0] > 0.0f && proj[5] > 0.0f;
@@ -2044,32 +2077,42 @@ __global__ __launch_bounds__(256) void k_ssao_mask(const slhip_scene* __restrict
     for (int k = threadIdx.x; k < TW * TH; k += 256) {
         const float2 t = T[k];
         const unsigned fl = __float_as_uint(t.y);
-        unsigned char sk = 0;
-        if (!(fl & 2u)) sk = 1;                                   // no geometry at all: every pixel is 1 anyway
+        int lvl = kSsaoLevels - 1, pass = 0;
+        if (!(fl & 2u)) { lvl = 0; pass = 1; }                    // no geometry at all: every pixel is 1 anyway
         else if (persp && !(fl & 1u) && t.x > 0.2f) {
-            const int R = (int)ceilf(reach / (t.x - 0.1f)) + 2;
-            const int x0 = (k % TW) * kSsaoTile - R, x1 = (k % TW) * kSsaoTile + kSsaoTile - 1 + R;
-            const int y0 = (k / TW) * kSsaoTile - R, y1 = (k / TW) * kSsaoTile + kSsaoTile - 1 + R;
-            if (x0 >= 0 && y0 >= 0 && x1 < W && y1 < H) {
+            // the boxes grow with rho: from the smallest up, until one leaves the image or touches something; last the full radius
+            for (int j = kSsaoLevels - 2; j >= -1; --j) {
+                const int R = (int)ceilf((j >= 0 ? kSsaoRho[j] : 1.0f) * reach / (t.x - 0.1f)) + 2;
+                const int x0 = (k % TW) * kSsaoTile - R, x1 = (k % TW) * kSsaoTile + kSsaoTile - 1 + R;
+                const int y0 = (k / TW) * kSsaoTile - R, y1 = (k / TW) * kSsaoTile + kSsaoTile - 1 + R;
+                if (!(x0 >= 0 && y0 >= 0 && x1 < W && y1 < H)) break;
                 const int ca = x0 / kSsaoTile, cb = x1 / kSsaoTile + 1, ra = y0 / kSsaoTile, rb = y1 / kSsaoTile + 1;
                 const int others = s_sat[rb * SW + cb] - s_sat[ra * SW + cb] - s_sat[rb * SW + ca] + s_sat[ra * SW + ca];
-                sk = others == 0 ? 1 : 0;
+                if (others != 0) break;
+                if (j >= 0) lvl = j;
+                else pass = 1;
             }
         }
-        S[k] = dbg == 1 ? 1 : dbg == 2 ? 0 : sk;
+        if (dbg == 1) { lvl = 0; pass = 1; }
+        if (dbg == 2) lvl = kSsaoLevels - 1;                      // every tile at the full list (bit 0 as it is: the same k_ssao_apply)
+        S[k] = (unsigned char)(lvl << 1 | pass);
     }
 }
 
-// grid: scenes x (H / 16) bands x 4 row classes; block = 4 waves = the 4 column classes of the same rows (their normal / position
-// fetches share cache lines)
+// grid: scenes x bands of `band_rows` rows x 4 row classes; block = 4 waves = the 4 column classes of the same rows (their normal /
+// position fetches share cache lines).  A wave scans its class's pixels once, 64 candidates at a time, and queues those that need
+// taps by the level of their tile (the pixel index only: the run reads the normal again); a queue that holds 64 runs its level's
+// list.  At the end of the band the remainders go, from the highest level down, into common runs of 64, each with the list of the
+// highest level in it: ONE partial run per wave, not one per level.
 __global__ __launch_bounds__(256) SLHIP_SSAO_KERNEL void k_ssao_tiled(const slhip_scene* __restrict__ scenes, unsigned n_scenes, int W, int H,
                                                     const float* __restrict__ cam, const float* __restrict__ nrm,
                                                     const float* __restrict__ zplane, float* __restrict__ ao,
-                                                    const float* __restrict__ kern, const unsigned char* __restrict__ skip)
+                                                    const float* __restrict__ level_kern, SsaoLevelCounts level_n,
+                                                    const unsigned char* __restrict__ skip, unsigned band_rows,
+                                                    unsigned* __restrict__ drain_stats)
 {
-    __shared__ unsigned s_q[4][128];
-    __shared__ float4 s_n[4][128];              // the queued pixels' normals (read once, in the scan)
-    const unsigned bands = (unsigned)H >> 4;
+    __shared__ unsigned s_q[4][kSsaoLevels - 1][128];       // per wave and level 1.. : < 64 waiting + the <= 64 of one scan
+    const unsigned bands = ((unsigned)H + band_rows - 1u) / band_rows;
     unsigned scene, rest;
     if (!scene_block(bands * 4u, n_scenes, scene, rest)) return;       // (all blocks of a scene on one XCD: its z plane in ONE L2)
     const unsigned band = rest >> 2, yc = rest & 3u, xc = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -2081,60 +2124,89 @@ __global__ __launch_bounds__(256) SLHIP_SSAO_KERNEL void k_ssao_tiled(const slhi
     const float4* N4 = reinterpret_cast<const float4*>(nrm) + (size_t)scene * P;
     const float4* C4 = reinterpret_cast<const float4*>(cam) + (size_t)scene * P;
     float* A = ao + (size_t)scene * P;
-    unsigned* q = s_q[xc];
-    float4* qn = s_n[xc];
-    const unsigned per_row = (unsigned)W >> 2, total = 4u * per_row;       // the class's pixels in the band: 4 rows x W / 4
-    unsigned count = 0;
-    auto run = [&](unsigned n_run) {
-        // the first n_run (<= 64) queued pixels
-        if (lane < n_run) {
-            const unsigned pix = q[lane];
-            const int i = (int)(pix % (unsigned)W), j = (int)(pix / (unsigned)W);
-            A[pix] = ssao_pixel(proj, camS, W, H, i, j, qn[lane], C4[pix], kern);
-        }
-    };
+    unsigned* q = &s_q[xc][0][0];                                         // level l at q + (l - 1) * 128
+    const unsigned y_first = band * band_rows, rows = min(band_rows, (unsigned)H - y_first);   // (multiples of 16)
+    const unsigned per_row = (unsigned)W >> 2, total = (rows >> 2) * per_row;   // the class's pixels in the band: rows / 4 x W / 4
+    unsigned cnt[kSsaoLevels] = {};                                       // (unrolled everywhere: scalar registers)
     // one chunk of candidates ahead: the loads of the next scan are in flight while the taps of the queue run
-    auto pixel_of = [&](unsigned ci) -> unsigned { return (band * 16u + yc + 4u * (ci / per_row)) * (unsigned)W + xc + 4u * (ci % per_row); };
-    auto fetch = [&](unsigned ci, unsigned& pix, bool& sk, float4& n4) {
-        pix = 0; sk = true; n4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    auto pixel_of = [&](unsigned ci) -> unsigned { return (y_first + yc + 4u * (ci / per_row)) * (unsigned)W + xc + 4u * (ci % per_row); };
+    auto fetch = [&](unsigned ci, unsigned& pix, unsigned& lvl, float4& n4) {
+        pix = 0; lvl = 0; n4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (ci < total) {
             pix = pixel_of(ci);
             const unsigned y = pix / (unsigned)W, x = pix % (unsigned)W;
-            sk = S[(y >> 3) * (unsigned)TW + (x >> 3)] != 0;
-            if (!sk) n4 = N4[pix];
+            const unsigned b = S[(y >> 3) * (unsigned)TW + (x >> 3)];
+            lvl = min(b >> 1, (unsigned)(kSsaoLevels - 1));
+            if (lvl) n4 = N4[pix];
         }
     };
-    unsigned pix_n; bool sk_n; float4 n4_n;
-    fetch(lane, pix_n, sk_n, n4_n);
-    for (unsigned c0 = 0; c0 < total; c0 += 64u) {
-        const unsigned pix = pix_n;
-        const bool sk = sk_n;
-        const float4 n4 = n4_n;
-        const bool valid = c0 + lane < total;
-        fetch(c0 + 64u + lane, pix_n, sk_n, n4_n);
-        const bool need = valid && !sk && !(n4.x == 0.0f && n4.y == 0.0f && n4.z == 0.0f);
-        if (valid && !need) A[pix] = 1.0f;
-        const unsigned long long m = __ballot(need);
-        if (need) {
-            const unsigned at = count + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-            q[at] = pix; qn[at] = n4;
+    unsigned pix_n, lvl_n; float4 n4_n;
+    fetch(lane, pix_n, lvl_n, n4_n);
+    unsigned c0 = 0;
+    for (;;) {
+        unsigned pix = 0, list = 0;
+        bool valid = false;
+#pragma unroll
+        for (int l = 1; l < kSsaoLevels; ++l)
+            if (cnt[l] >= 64u) list = (unsigned)l;
+        if (list) {
+            // a full run of one level (the newest 64 of its queue)
+#pragma unroll
+            for (int l = 1; l < kSsaoLevels; ++l)
+                if (list == (unsigned)l) { cnt[l] -= 64u; pix = q[(l - 1) * 128 + cnt[l] + lane]; }
+            valid = true;
+        } else if (c0 < total) {
+            // scan the next 64 candidates
+            const unsigned px = pix_n, lvl = lvl_n;
+            const float4 n4 = n4_n;
+            const bool in = c0 + lane < total;
+            c0 += 64u;
+            fetch(c0 + lane, pix_n, lvl_n, n4_n);
+            const bool need = in && lvl != 0u && !(n4.x == 0.0f && n4.y == 0.0f && n4.z == 0.0f);
+            if (in && !need) A[px] = 1.0f;
+#pragma unroll
+            for (int l = 1; l < kSsaoLevels; ++l) {
+                const bool mine = need && lvl == (unsigned)l;
+                const unsigned long long m = __ballot(mine);
+                if (mine) q[(l - 1) * 128 + cnt[l] + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = px;
+                cnt[l] += (unsigned)__popcll(m);
+            }
+            __builtin_amdgcn_wave_barrier();
+            continue;
+        } else {
+            // the end of the band: what is left, from the highest level down, 64 at a time
+            unsigned room = 64u, p = lane, lowest = 0;
+#pragma unroll
+            for (int l = kSsaoLevels - 1; l >= 1; --l) {
+                const unsigned take = min(cnt[l], room);
+                if (take) {
+                    if (!list) list = (unsigned)l;
+                    lowest = (unsigned)l;
+                    cnt[l] -= take;
+                    room -= take;
+                    if (!valid) {
+                        if (p < take) { pix = q[(l - 1) * 128 + cnt[l] + p]; valid = true; }
+                        else p -= take;
+                    }
+                }
+            }
+            if (!list) break;
+            if (drain_stats && lane == 0u) {                             // (only when asked for: SLHIP_SSAO_DEBUG=3)
+                atomicAdd(&drain_stats[0], 1u);
+                if (lowest != list) atomicAdd(&drain_stats[1], 1u);       // levels mixed in one run
+            }
         }
-        count += (unsigned)__popcll(m);
         __builtin_amdgcn_wave_barrier();
-        if (count >= 64u) {
-            run(64u);
-            __builtin_amdgcn_wave_barrier();
-            const unsigned left = count - 64u;
-            unsigned mv = 0;
-            float4 mn = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (lane < left) { mv = q[64u + lane]; mn = qn[64u + lane]; }
-            __builtin_amdgcn_wave_barrier();
-            if (lane < left) { q[lane] = mv; qn[lane] = mn; }
-            count = left;
-            __builtin_amdgcn_wave_barrier();
+        int n_taps = 0;
+#pragma unroll
+        for (int l = 1; l < kSsaoLevels; ++l)
+            if (list == (unsigned)l) n_taps = level_n.n[l];
+        if (valid) {
+            const int i = (int)(pix % (unsigned)W), j = (int)(pix / (unsigned)W);
+            A[pix] = ssao_pixel(proj, camS, W, H, i, j, N4[pix], C4[pix], level_kern + 192u * list, n_taps);
         }
+        __builtin_amdgcn_wave_barrier();
     }
-    if (count > 0u) run(count);
 }
 
 // ... and the tone map of the result in the same pass (tone_map_shader.frag after ssao_apply_shader.frag): the blurred-AO colour
@@ -2162,7 +2234,7 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_ssao_apply(const slh
         const int TW = W / kSsaoTile;
         const unsigned char* S = skip + (size_t)scene * ((size_t)TW * (H / kSsaoTile));
         const int xa = max(i - 2, 0) >> 3, xb = min(i + 1, W - 1) >> 3, ya = max(j - 2, 0) >> 3, yb = min(j + 1, H - 1) >> 3;
-        const bool ones = (S[ya * TW + xa] & S[ya * TW + xb] & S[yb * TW + xa] & S[yb * TW + xb]) != 0;
+        const bool ones = (S[ya * TW + xa] & S[ya * TW + xb] & S[yb * TW + xa] & S[yb * TW + xb] & 1) != 0;   // bit 0: open plane at the full radius
         if (__all(ones)) {
             const float4 h = reinterpret_cast<const float4*>(hdr_in)[gp];
             const float c4[4] = {h.x, h.y, h.z, h.w};
@@ -2354,12 +2426,64 @@ extern "C" int slhip_render_timings(float* ms_out)
 // ssao_shader.cpp:72-112)
 #include "ssao_tables.inc"
 
-// layout of d_ao: [B][H][W] occlusion, [B][H + 2][W + 2] camera z, then (8-byte aligned) the SSAO tile records and skip bytes
+// The level lists of k_ssao_mask / k_ssao_tiled, derived once from the kernel table: list j holds, in ascending k, every sample
+// with 1.001 |s_k| > rho_j (lengths in double); list 0 is empty as long as rho_0 covers the longest sample, the last list is 0..63.
+namespace {
+struct SsaoLevelTables {
+    float kern[kSsaoLevels * 192];
+    uint8_t taps[kSsaoLevels * 64];
+    SsaoLevelCounts count;
+};
+const SsaoLevelTables& ssao_level_tables()
+{
+    static const SsaoLevelTables tables = [] {
+        SsaoLevelTables t = {};
+        for (int j = 0; j < kSsaoLevels; ++j) {
+            int n = 0;
+            for (int k = 0; k < 64; ++k) {
+                const double x = k_ssao_kernel_host[3 * k], y = k_ssao_kernel_host[3 * k + 1], z = k_ssao_kernel_host[3 * k + 2];
+                if (j < kSsaoLevels - 1 && !(1.001 * std::sqrt(x * x + y * y + z * z) > (double)kSsaoRho[j])) continue;
+                for (int c = 0; c < 3; ++c) t.kern[j * 192 + 3 * n + c] = k_ssao_kernel_host[3 * k + c];
+                t.taps[j * 64 + n] = (uint8_t)k;
+                ++n;
+            }
+            t.count.n[j] = n;
+        }
+        return t;
+    }();
+    return tables;
+}
+}  // namespace
+
+// The level thresholds and lists (measurement / test read-out): rho[5], counts[6], taps[6 * 64] (list j at taps + 64 j, its first
+// counts[j] entries).
+extern "C" int slhip_render_ssao_level_tables(float rho[5], uint32_t counts[6], uint8_t taps[384])
+{
+    if (!rho || !counts || !taps) {
+        slhip::set_error("slhip_render_ssao_level_tables: null argument");
+        return -1;
+    }
+    const SsaoLevelTables& t = ssao_level_tables();
+    for (int j = 0; j < kSsaoLevels - 1; ++j) rho[j] = kSsaoRho[j];
+    for (int j = 0; j < kSsaoLevels; ++j) counts[j] = (uint32_t)t.count.n[j];
+    memcpy(taps, t.taps, sizeof(t.taps));
+    return 0;
+}
+
+// layout of d_ao: [B][H][W] occlusion, [B][H + 2][W + 2] camera z, then (8-byte aligned) the SSAO tile records and skip bytes, then
+// (in the 16 spare bytes, 8-byte aligned) two counters of k_ssao_tiled: end-of-band runs, those of them with levels mixed
 static inline uint64_t ssao_tiles_per_scene(uint32_t w, uint32_t h) { return (uint64_t)((w + 7) / 8) * ((h + 7) / 8); }
 static inline uint64_t ssao_tiles_offset(uint64_t B, uint32_t w, uint32_t h)
 {
     const uint64_t b = B * (uint64_t)w * h * 4 + B * (uint64_t)(w + 2) * (h + 2) * 4;
     return (b + 7u) & ~(uint64_t)7u;
+}
+
+constexpr uint64_t kSsaoScratchSpare = 16;      // bytes of d_ao behind the tile bytes
+static_assert(7 + 2 * sizeof(unsigned) <= kSsaoScratchSpare, "the two counters of k_ssao_tiled, 8-byte aligned, live in the spare bytes");
+static inline uint64_t ssao_stats_offset(uint64_t B, uint32_t w, uint32_t h)
+{
+    return (ssao_tiles_offset(B, w, h) + B * ssao_tiles_per_scene(w, h) * 9 + 7u) & ~(uint64_t)7u;
 }
 
 extern "C" int slhip_render_scratch_bytes(uint32_t n_scenes, uint32_t width, uint32_t height,
@@ -2370,7 +2494,7 @@ extern "C" int slhip_render_scratch_bytes(uint32_t n_scenes, uint32_t width, uin
     bytes_out[0] = B * P * 8;                                              // d_vis
     bytes_out[1] = 2 * B * P * 16;                                         // d_hdr (two planes)
     // d_ao + padded camera-z plane + (k_ssao_mask) per 8 x 8 tile: float2 record, skip byte
-    bytes_out[2] = ssao_tiles_offset(B, width, height) + B * ssao_tiles_per_scene(width, height) * 9 + 16;
+    bytes_out[2] = ssao_tiles_offset(B, width, height) + B * ssao_tiles_per_scene(width, height) * 9 + kSsaoScratchSpare;
     bytes_out[3] = B * SLHIP_NUM_LIGHTS * (uint64_t)shadow_res * shadow_res * 4;  // d_shadow
     bytes_out[4] = 16 + (uint64_t)queue_capacity * 16;                     // d_queue
     bytes_out[5] = B * blocks * 16;                                        // d_lum
@@ -2379,7 +2503,8 @@ extern "C" int slhip_render_scratch_bytes(uint32_t n_scenes, uint32_t width, uin
 }
 
 // How much of the last SSAO pass on this scratch was skipped (k_ssao_mask): 8 x 8 tiles in all, tiles whose occlusion is 1 without
-// running the taps.  Synchronises `stream`.  counts = {0, 0} when the pass did not run tiled (viewport not a multiple of 32 x 16).
+// running the taps at the full radius (bit 0 of the tile byte: what k_ssao_apply hands through; level 0 holds some more).
+// Synchronises `stream`.  counts = {0, 0} when the pass did not run tiled (viewport not a multiple of 32 x 16).
 extern "C" int slhip_render_ssao_skipped(const slhip_render_scratch* scratch, uint32_t n_scenes, uint32_t width, uint32_t height,
                                          uint64_t counts[2], void* stream_)
 {
@@ -2396,8 +2521,41 @@ extern "C" int slhip_render_ssao_skipped(const slhip_render_scratch* scratch, ui
     SLHIP_CHECK(hipMemcpyAsync(h.data(), base, nt, hipMemcpyDeviceToHost, stream));
     SLHIP_CHECK(hipStreamSynchronize(stream));
     counts[0] = nt;
-    for (unsigned char b : h) counts[1] += b ? 1 : 0;
+    for (unsigned char b : h) counts[1] += b & 1;
     return 0;
+}
+
+// The same pass by level: counts[0..5] = tiles of level 0 (no taps) .. 5 (all taps), counts[6] = end-of-band runs of k_ssao_tiled,
+// counts[7] = those of them that held pixels of more than one level (both counted only under SLHIP_SSAO_DEBUG=3).  Synchronises `stream`; all zero when the pass did not run tiled.
+extern "C" int slhip_render_ssao_levels(const slhip_render_scratch* scratch, uint32_t n_scenes, uint32_t width, uint32_t height,
+                                        uint64_t counts[8], void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!scratch || !scratch->d_ao || !counts) {
+        slhip::set_error("slhip_render_ssao_levels: null argument");
+        return -1;
+    }
+    for (int i = 0; i < 8; ++i) counts[i] = 0;
+    if (width % 32 != 0 || height % 16 != 0 || n_scenes == 0) return 0;
+    const uint64_t nt = (uint64_t)n_scenes * ssao_tiles_per_scene(width, height);
+    std::vector<unsigned char> h(nt);
+    unsigned stats[2] = {0, 0};
+    const char* ao = reinterpret_cast<const char*>(scratch->d_ao);
+    SLHIP_CHECK(hipMemcpyAsync(h.data(), ao + ssao_tiles_offset(n_scenes, width, height) + nt * 8, nt, hipMemcpyDeviceToHost, stream));
+    SLHIP_CHECK(hipMemcpyAsync(stats, ao + ssao_stats_offset(n_scenes, width, height), sizeof(stats), hipMemcpyDeviceToHost, stream));
+    SLHIP_CHECK(hipStreamSynchronize(stream));
+    for (unsigned char b : h) counts[std::min<int>(b >> 1, kSsaoLevels - 1)] += 1;
+    counts[6] = stats[0];
+    counts[7] = stats[1];
+    return 0;
+}
+
+constexpr int kSsaoBandRows = 16;   // measured at 16 / 32 / 48 rows on the C2 shape: SSAO 13.0 / 14.2 / 15.0 ms per 1024 scenes (profiles/r07)
+static unsigned ssao_band_rows_knob()
+{
+    const char* e = getenv("SLHIP_SSAO_BAND_ROWS");
+    const int v = e ? atoi(e) : kSsaoBandRows;
+    return (unsigned)std::min(std::max(16, v / 16 * 16), 1 << 16);
 }
 
 extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_scenes, const slhip_draw* d_draws,
@@ -2464,6 +2622,12 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
                                                hipMemcpyHostToDevice, stream));
             SLHIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_ssao_kernel), k_ssao_kernel_host, sizeof(float) * 192, 0,
                                                hipMemcpyHostToDevice, stream));
+            const SsaoLevelTables& lt = ssao_level_tables();
+            if (lt.count.n[0] != 0) {
+                slhip::set_error("slhip_render: the first SSAO level threshold does not cover the longest kernel sample");
+                return -1;
+            }
+            SLHIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_ssao_level_kernel), lt.kern, sizeof(lt.kern), 0, hipMemcpyHostToDevice, stream));
             g_ssao_tables_uploaded[dev] = true;
         }
     }
@@ -2566,9 +2730,20 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
             const float* d_kernel_table = nullptr;   // the table's device address as a plain kernel argument
             SLHIP_CHECK(hipGetSymbolAddress((void**)&d_kernel_table, HIP_SYMBOL(c_ssao_kernel)));
             if (ssao_tiled) {
-                k_ssao_mask<<<n_scenes, 256, (size_t)(W / 8 + 1) * (H / 8 + 1) * 4, stream>>>(d_scenes, W, H, ssao_tiles, ssao_skip, getenv("SLHIP_SSAO_DEBUG") ? atoi(getenv("SLHIP_SSAO_DEBUG")) : 0);
-                k_ssao_tiled<<<8u * ((n_scenes + 7u) / 8u) * (unsigned)(H / 16) * 4u, 256, 0, stream>>>(d_scenes, n_scenes, W, H, out->d_cam_coord, out->d_normals,
-                                                                                   zpl, scratch->d_ao, d_kernel_table, ssao_skip);
+                // rows per band of k_ssao_tiled: deeper bands fill the level queues' runs better (SLHIP_SSAO_BAND_ROWS, a developer
+                // knob read at every call: a multiple of 16, default kSsaoBandRows)
+                const unsigned band_rows = ssao_band_rows_knob();
+                const int ssao_dbg = getenv("SLHIP_SSAO_DEBUG") ? atoi(getenv("SLHIP_SSAO_DEBUG")) : 0;
+                const unsigned bands = ((unsigned)H + band_rows - 1u) / band_rows;
+                unsigned* drain_stats = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(scratch->d_ao) + ssao_stats_offset(n_scenes, W, H));
+                const float* d_level_table = nullptr;
+                SLHIP_CHECK(hipGetSymbolAddress((void**)&d_level_table, HIP_SYMBOL(c_ssao_level_kernel)));
+                // SLHIP_SSAO_DEBUG (read at every call): 1 = every tile skipped, 2 = every tile at the full list, 3 = the levels as they
+                // are, and k_ssao_tiled counts its end-of-band runs (slhip_render_ssao_levels; atomics no other render pays for)
+                k_ssao_mask<<<n_scenes, 256, (size_t)(W / 8 + 1) * (H / 8 + 1) * 4, stream>>>(d_scenes, W, H, ssao_tiles, ssao_skip, ssao_dbg, drain_stats);
+                k_ssao_tiled<<<8u * ((n_scenes + 7u) / 8u) * bands * 4u, 256, 0, stream>>>(d_scenes, n_scenes, W, H, out->d_cam_coord, out->d_normals,
+                                                                                   zpl, scratch->d_ao, d_level_table, ssao_level_tables().count, ssao_skip,
+                                                                                   band_rows, ssao_dbg == 3 ? drain_stats : nullptr);
             } else
                 k_ssao<<<pix_blocks, 256, 0, stream>>>(d_scenes, n_scenes, W, H, out->d_cam_coord, out->d_normals, zpl, scratch->d_ao,
                                                        d_kernel_table);

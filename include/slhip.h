@@ -653,6 +653,62 @@ typedef struct {
 int slhip_camera_model(const float* d_in, float* d_out, float* d_tmp, uint32_t n_images, int H, int W,
                        const slhip_camera_params* d_params, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depth sensor model: the depth sibling of the camera model.  This project's addition -- the
+ * reference has no counterpart (its camera_model.py treats the colour image only).  It turns the
+ * rasteriser's exact camera z into what a rectified structured-light / active-stereo sensor
+ * (projector at +baseline along camera x) delivers: range limits, holes at grazing angles, the
+ * projector's shadow band beside every object, holes where the matching window straddles a
+ * discontinuity, lateral jitter, disparity noise, 1/subpixel px disparity quantisation, dropout.
+ * Two kernels: pass 1 builds one projector line per image row in LDS and writes a disparity and a
+ * flag plane to scratch; pass 2 works on 32 x 8 tiles with a halo of 2 + window_radius in LDS.
+ * DESIGN.md "Depth sensor model" states the model step by step; tests/depth_sensor_ref.py restates
+ * it in NumPy in the same operation order.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_DEPTH_FLAG_RANGE    1u   /* z outside [z_min, z_max] or NaN; noisy disparity <= 0 */
+#define SLHIP_DEPTH_FLAG_GRAZING  2u   /* |n.v| < cos_min                                       */
+#define SLHIP_DEPTH_FLAG_SHADOW   4u   /* the projector does not see the surface                */
+#define SLHIP_DEPTH_FLAG_SUPPORT  8u   /* fewer than min_support window pixels agree            */
+#define SLHIP_DEPTH_FLAG_DROPOUT  16u  /* random dropout                                        */
+#define SLHIP_DEPTH_SENSOR_MAX_LINE   4096   /* W + Dmax, Dmax = ceil(fb / z_min): the projector line in LDS */
+#define SLHIP_DEPTH_SENSOR_MAX_RADIUS 4
+
+typedef struct {
+    float fb;               /* fx * baseline (px * m), rounded once to f32 on the host             */
+    float z_min, z_max;     /* working range of the sensor, metres                                 */
+    float shadow_margin;    /* px of disparity an occluder must be in front by to cast a shadow     */
+    float cos_min;          /* grazing limit on |n.v|; 0 switches the stage off                    */
+    uint32_t window_radius; /* r of the (2r+1)^2 matching window, 0..4                             */
+    float window_tol;       /* px of disparity within which a window pixel supports the centre     */
+    uint32_t min_support;   /* fewer supporting pixels (the centre counts) -> SUPPORT              */
+    float sigma_lateral;    /* px; the source pixel is jittered by round(sigma * N(0,1)), +-2 at most */
+    float sigma_disparity;  /* px of Gaussian noise on the disparity                               */
+    uint32_t subpixel;      /* quantisation steps per px of disparity; 0 = none                    */
+    float dropout_p;        /* probability of a random hole                                        */
+    float depth_scale;      /* millimetres per unit of the uint16 output (BOP's depth_scale)       */
+    uint32_t seed_lo, seed_hi; /* counter-based RNG key of this image                              */
+} slhip_depth_sensor_params;   /* 60 bytes */
+
+/* Host-side check of n_images HOST records against an image width: fb, z_min, depth_scale > 0, z_max >= z_min,
+ * window_radius <= 4, W + ceil(fb / z_min) <= 4096.  Needs no device.  slhip_depth_sensor reads its records on the device and
+ * cannot fail on them: an image whose record breaks a limit comes out all RANGE (flags 1, depth 0).   */
+int slhip_depth_sensor_check_params(const slhip_depth_sensor_params* h_params, uint32_t n_images, int W);
+/* bytes of d_scratch: the disparity plane f32 [n,H,W] followed by the flag plane u8 [n,H,W].  Needs no device. */
+int slhip_depth_sensor_scratch_bytes(uint32_t n_images, int W, int H, uint64_t* bytes);
+/* d_depth: z of pixel (i, y, x) at d_depth[((i * H + y) * W + x) * depth_stride] (stride in floats: 4 for the w of
+ * slhip_render_out.d_coord, 1 for a dense plane); d_ndotv likewise (the w of d_normals), NULL = no grazing stage.
+ * d_params: DEVICE array of n_images records.  Outputs, each NULL when not wanted: d_out_f32 f32 [n,H,W] metres, 0 where
+ * invalid; d_out_u16 u16 [n,H,W] = min(65535, floor(z * 1000 / depth_scale + 0.5)), 0 where invalid; d_flags u8 [n,H,W],
+ * SLHIP_DEPTH_FLAG_* bits, 0 = valid.  d_scratch: slhip_depth_sensor_scratch_bytes, 16-byte aligned; the inputs must not
+ * alias the outputs.  Asynchronous on `stream`.                                                     */
+int slhip_depth_sensor(const float* d_depth, uint32_t depth_stride, const float* d_ndotv, uint32_t ndotv_stride,
+                       uint32_t n_images, int H, int W, const slhip_depth_sensor_params* d_params, float* d_out_f32,
+                       uint16_t* d_out_u16, uint8_t* d_flags, void* d_scratch, void* stream);
+/* Developer hook (tools/time_depth_sensor.py): with timing on, a call records HIP events around its two passes;
+ * slhip_depth_sensor_timings waits for the last timed call and gives ms_out[0] = pass 1, ms_out[1] = pass 2.   */
+int slhip_depth_sensor_timing_enable(int on);
+int slhip_depth_sensor_timings(float ms_out[2]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).

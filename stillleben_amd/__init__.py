@@ -25,13 +25,14 @@ from .object_stats import ObjectStats  # noqa: F401  (additive: per-object visib
 from .object_masks import ObjectMasks  # noqa: F401  (additive: per-object masks, BOP's mask/, mask_visib/ and scene_gt_coco)
 from . import camera_model, diff, losses, extension, profiling  # noqa: F401
 from . import bop  # noqa: F401  (additive: BOP scene_camera / scene_gt entries from a SceneBatch's records)
+from . import depth_sensor  # noqa: F401  (additive: the depth channel's sensor model, the sibling of camera_model)
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
     'Mesh', 'MeshCache', 'Object', 'Range3D', 'RenderPass', 'RenderPassResult', 'Scene', 'Texture',
     'Texture2D', 'Viewer', 'view', 'ManipulationSim', 'JobQueue', 'AssetTable', 'SceneBatch',
     'camera_model', 'diff', 'extension', 'losses', 'quat_to_matrix', 'matrix_to_quat', 'ObjectStats', 'ObjectMasks', 'EnvironmentBank',
-    'bop',
+    'bop', 'depth_sensor',
 ]
 
 

@@ -207,6 +207,14 @@ CAMERA_DTYPE = np.dtype([
     ("blur_enabled", np.uint32), ("noise_enabled", np.uint32), ("seed_lo", np.uint32), ("seed_hi", np.uint32),
 ])
 assert CAMERA_DTYPE.itemsize == 268
+# slhip_depth_sensor_params (include/slhip.h), 60 bytes
+DEPTH_SENSOR_DTYPE = np.dtype([
+    ("fb", np.float32), ("z_min", np.float32), ("z_max", np.float32), ("shadow_margin", np.float32), ("cos_min", np.float32),
+    ("window_radius", np.uint32), ("window_tol", np.float32), ("min_support", np.uint32), ("sigma_lateral", np.float32),
+    ("sigma_disparity", np.float32), ("subpixel", np.uint32), ("dropout_p", np.float32), ("depth_scale", np.float32),
+    ("seed_lo", np.uint32), ("seed_hi", np.uint32),
+])
+assert DEPTH_SENSOR_DTYPE.itemsize == 60
 
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
@@ -362,6 +370,13 @@ def lib():
     L.slhip_light_map_floats.argtypes = [C.c_uint32] * 6 + [C.POINTER(C.c_uint64 * 4)]
     L.slhip_light_map_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.slhip_camera_model.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(L, "slhip_depth_sensor"):             # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_depth_sensor_check_params.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
+        L.slhip_depth_sensor_timing_enable.argtypes = [C.c_int]
+        L.slhip_depth_sensor_timings.argtypes = [C.POINTER(C.c_float * 2)]
+        L.slhip_depth_sensor_scratch_bytes.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.slhip_depth_sensor.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

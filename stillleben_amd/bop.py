@@ -51,6 +51,12 @@ def scene_camera_entry(intrinsics, camera_pose, depth_scale=1.0):
             "depth_scale": float(depth_scale)}
 
 
+def depth_image_scale(z_max):
+    """The finest `depth_scale` (millimetres per unit) with which depths up to `z_max` metres fit BOP's uint16 depth image:
+    z_max lands on 65535.  Give it to sl.depth_sensor.make_params and to scene_camera_entry alike."""
+    return float(z_max) * MM / 65535.0
+
+
 def scene_gt_entries(object_to_camera, mesh_to_object, class_indices):
     """One image's list of scene_gt.json, in slot order (entry i = the object with instance index i + 1, as
     ObjectStats.to_bop lists them).  `object_to_camera`: [n_objects, 3, 4] (SceneBatch.object_to_camera[b]);

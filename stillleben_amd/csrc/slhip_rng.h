@@ -1,0 +1,75 @@
+// slhip_rng.h -- counter-based RNG of the sensor models (slhip_camera.hip, slhip_depth_sensor.hip): Philox4x32-10 keyed by
+// the image's seed, counted by (pixel, image), with the uniform / normal / Poisson draws on top.  Device code only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace slhip {
+
+struct Philox {
+    uint32_t c[4], k[2];
+    __device__ void round()
+    {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1];
+        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
+        k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
+    }
+    __device__ void block()
+    {
+#pragma unroll
+        for (int i = 0; i < 10; ++i) round();
+    }
+};
+
+struct Rng {
+    uint32_t key0, key1, ctr0, ctr1, sub;
+    uint32_t buf[4];
+    int left;
+    __device__ Rng(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1) : key0(k0), key1(k1), ctr0(c0), ctr1(c1), sub(0), left(0) {}
+    __device__ uint32_t next()
+    {
+        if (left == 0) {
+            Philox p;
+            p.c[0] = ctr0; p.c[1] = ctr1; p.c[2] = sub++; p.c[3] = 0x5114EBE2u;
+            p.k[0] = key0; p.k[1] = key1;
+            p.block();
+            buf[0] = p.c[0]; buf[1] = p.c[1]; buf[2] = p.c[2]; buf[3] = p.c[3];
+            left = 4;
+        }
+        return buf[--left];
+    }
+    __device__ float uniform() { return ((float)(next() >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0,1)
+    __device__ float normal()
+    {
+        const float u1 = uniform(), u2 = uniform();
+        return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+    }
+    // Poisson(lambda): multiplication method below 10, Hoermann's transformed rejection (PTRS) above
+    __device__ float poisson(float lambda)
+    {
+        if (!(lambda > 0.0f)) return 0.0f;
+        if (lambda < 10.0f) {
+            const float limit = expf(-lambda);
+            float prod = uniform();
+            int k = 0;
+            while (prod > limit && k < 200) { prod *= uniform(); ++k; }
+            return (float)k;
+        }
+        const float slam = sqrtf(lambda), loglam = logf(lambda);
+        const float b = 0.931f + 2.53f * slam, a = -0.059f + 0.02483f * b;
+        const float inv_alpha = 1.1239f + 1.1328f / (b - 3.4f), vr = 0.9277f - 3.6224f / (b - 2.0f);
+        for (int it = 0; it < 64; ++it) {
+            const float U = uniform() - 0.5f, V = uniform();
+            const float us = 0.5f - fabsf(U);
+            const float k = floorf((2.0f * a / us + b) * U + lambda + 0.43f);
+            if (us >= 0.07f && V <= vr) return k;
+            if (k < 0.0f || (us < 0.013f && V > us)) continue;
+            if (logf(V) + logf(inv_alpha) - logf(a / (us * us) + b) <= -lambda + k * loglam - lgammaf(k + 1.0f)) return k;
+        }
+        return floorf(lambda + 0.5f);
+    }
+};
+
+}  // namespace slhip

@@ -44,7 +44,8 @@ extern "C" {
                                     slhip_host_fill_holes
                                  5, additive (no struct or signature changed; detect with dlsym): slhip_object_stats,
                                     slhip_render_object_stats, slhip_render_object_stats_bytes; slhip_object_mask,
-                                    slhip_render_object_masks, slhip_render_object_masks_bytes, slhip_object_masks_expand       */
+                                    slhip_render_object_masks, slhip_render_object_masks_bytes, slhip_object_masks_expand;
+                                    slhip_object_crops_check_params, _scratch_bytes, _select, _gather, _timing_enable, _timings */
 #define SLHIP_NUM_LIGHTS 3 /* reference include/stillleben/common.h:17 */
 
 /* ---------------------------------------------------------------------------------------------
@@ -709,6 +710,93 @@ int slhip_depth_sensor(const float* d_depth, uint32_t depth_stride, const float*
 int slhip_depth_sensor_timing_enable(int on);
 int slhip_depth_sensor_timings(float ms_out[2]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Object crops: one fixed-size square window per visible object of a render, the input of an
+ * object-centric network ("dynamic zoom-in": the object's 2D box, enlarged, randomly scaled and
+ * shifted).  This project's addition, the reference has no counterpart.  Two steps on the device:
+ * slhip_object_crops_select turns the statistics of a render (slhip_object_stats) into a compact
+ * list of crop records in ascending (scene, slot) order; slhip_object_crops_gather resamples the
+ * render targets into N x N windows, one thread per output pixel.  All arithmetic is float32, one
+ * rounded IEEE operation at a time (no fma); tests/object_crops_ref.py restates it in NumPy bit
+ * for bit.  DESIGN.md "Object crops" states the rules.
+ *
+ * Eligible: the chosen box is non-empty, px_visib >= min_px, (float)px_visib >= min_visib_fract *
+ * (float)px_all; slot 0 never.  With (x, y, w, h) the chosen box and u0, u1, u2 the first three
+ * uniforms of stream 5 ("Randomness" below; the draw is always made):
+ *   side = (float)max(w, h) * pad * (1 + jitter_scale * (2 u0 - 1))
+ *   cx_b = (float)x + 0.5 (float)w + jitter_shift * (float)w * (2 u1 - 1)      (cy_b likewise, h and u2)
+ *   x0 = cx_b - 0.5 side, y0 = cy_b - 0.5 side, step = side / (float)N
+ *   K' = (fx / step, fy / step, (cx - x0) / step, (cy - y0) / step)
+ * Output pixel (u, v) samples the picture at sx = x0 + ((float)u + 0.5) step, sy likewise (image x runs from edge 0 to edge W,
+ * pixel j covers [j, j + 1)).  Everything but rgb takes the NEAREST pixel (floor(sx), floor(sy)), 0 outside the picture.
+ * rgb is BILINEAR on all four bytes: tx = sx - 0.5, ix = floor(tx), ax = tx - ix (y likewise), taps outside count as 0,
+ * top = (1 - ax) p00 + ax p10, bot = (1 - ax) p01 + ax p11, val = (1 - ay) top + ay bot, byte = min(255, floor(val + 0.5)).
+ * There is no anti-aliasing filter for step > 1 (a window larger than N source pixels is point-sampled).
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_CROP_RGB      1u    /* u8  [n,N,N,4] */
+#define SLHIP_CROP_COORD    2u    /* f32 [n,N,N,4] object xyz, camera z */
+#define SLHIP_CROP_NORMALS  4u    /* f32 [n,N,N,4] */
+#define SLHIP_CROP_INSTANCE 8u    /* i16 [n,N,N]   */
+#define SLHIP_CROP_MASK     16u   /* u8  [n,N,N]: bit 0 visible (the nearest sample's instance output is the slot), bit 1
+                                     amodal (the kind-0 bit of the slot's tiles at the nearest sample; 0 without masks) */
+#define SLHIP_OBJECT_CROPS_MAX_SIZE 1024
+#define SLHIP_OBJECT_CROPS_CAPACITY 3   /* status of slhip_object_crops_select: d_crops is too small */
+
+typedef struct {
+    uint32_t size;             /* N: the windows are N x N, 1..1024                                         */
+    uint32_t box;              /* 0: bbox_visib, 1: bbox_obj                                                */
+    float pad;                 /* side of the window / longer side of the box, > 0                         */
+    float jitter_scale;        /* [0, 1): the side is scaled by 1 +- this                                   */
+    float jitter_shift;        /* [0, 1]: the centre moves by +- this share of the box's width / height     */
+    uint32_t min_px;           /* >= 1: fewer visible pixels -> no crop                                      */
+    float min_visib_fract;     /* [0, 1]: a smaller visible share of the silhouette -> no crop               */
+    float fx, fy, cx, cy;      /* intrinsics the picture was rendered with (Scene.set_camera_intrinsics)     */
+    uint32_t seed_lo, seed_hi; /* Philox key of the jitter                                                   */
+    uint32_t scene_id_base;    /* scene id of scene 0 of d_stats                                            */
+    uint32_t outputs;          /* SLHIP_CROP_* bits, at least one                                           */
+    uint32_t isolate;          /* 1: coord and normals are zero wherever mask bit 0 is clear                */
+} slhip_object_crop_params;    /* 64 bytes */
+
+typedef struct {
+    uint32_t scene, slot;
+    float x0, y0, side, step;  /* the window's top-left corner, side and source pixels per output pixel    */
+    float K[4];                /* fx', fy', cx', cy' of the window                                          */
+    uint32_t _pad[2];
+} slhip_object_crop;           /* 48 bytes */
+
+typedef struct {               /* outputs of slhip_object_crops_gather; those not named in `outputs` are not touched */
+    uint8_t* d_rgb;
+    float*   d_coord;
+    float*   d_normals;
+    int16_t* d_instance;
+    uint8_t* d_mask;
+} slhip_object_crops_out;
+
+/* Every rule of the parameter record against a W x H picture; a negative error with slhip_last_error text.  No device. */
+int slhip_object_crops_check_params(const slhip_object_crop_params* params, int W, int H);
+/* bytes of the d_scratch of slhip_object_crops_select (8-byte aligned).  No device. */
+int slhip_object_crops_scratch_bytes(uint32_t n_scenes, uint64_t* bytes);
+/* d_stats: slhip_object_stats [n_scenes][n_slots] (device).  Writes the records of all eligible (scene, slot), slot >= 1, in
+ * ascending (scene, slot) order to d_crops (device, `capacity` records; n_scenes * (n_slots - 1) always suffices) and their
+ * number to *n_out (host).  Returns 0, SLHIP_OBJECT_CROPS_CAPACITY when the number exceeds `capacity` (*n_out is still the
+ * needed count; nothing is promised about d_crops), or a negative error.  Synchronises `stream` once.                   */
+int slhip_object_crops_select(const slhip_object_crop_params* params, const slhip_object_stats* d_stats, uint32_t n_scenes,
+                              uint32_t n_slots, int W, int H, slhip_object_crop* d_crops, uint64_t capacity, void* d_scratch,
+                              uint64_t* n_out, void* stream);
+/* buffers: the render targets of the picture ([n_scenes,H,W,...]); only those a requested output reads must be non-NULL
+ * (d_rgb, d_coord, d_normals; d_instance for SLHIP_CROP_INSTANCE, SLHIP_CROP_MASK and isolate).  d_masks / d_words: the records
+ * and bit tiles of slhip_render_object_masks of the same picture, or both NULL (mask bit 1 then stays 0).  A record whose
+ * scene or slot lies outside [n_scenes][n_slots] gives an all-zero window.  n_crops == 0 returns 0 without a launch.
+ * Asynchronous on `stream`.                                                                                              */
+int slhip_object_crops_gather(const slhip_object_crop_params* params, const slhip_object_crop* d_crops, uint64_t n_crops,
+                              const slhip_render_out* buffers, uint32_t n_scenes, int W, int H,
+                              const slhip_object_mask* d_masks, const uint64_t* d_words, uint32_t n_slots,
+                              const slhip_object_crops_out* out, void* stream);
+/* Developer hook (tools/time_object_crops.py): with timing on, the two calls record HIP events around their kernels;
+ * slhip_object_crops_timings waits for them and gives ms_out[0] = the last select, ms_out[1] = the last gather.   */
+int slhip_object_crops_timing_enable(int on);
+int slhip_object_crops_timings(float ms_out[2]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).
@@ -760,6 +848,8 @@ int slhip_stream_destroy(void* stream);
  * roughness, 4 environment (slhip_synth_place_env only; no draw of streams 0-3 depends on it).  Stream 4, index 0:
  * x[0] gates the light set, x[1] picks it, x[2] gates the background image, x[3] picks it; index 1: x[0] gates the plane
  * texture, x[1] picks it.  Gate: uniform(x) < p.  Pick: min(n - 1, (uint32_t)(uniform(x) * (float)n)), float32 throughout.
+ * Stream 5, crop jitter (slhip_object_crops_select only; its key and scene id base are the caller's): index = the slot,
+ * x[0] scales the window, x[1] and x[2] shift it along x and y.
  * Views (slhip_synth_place_view): azimuth and elevation of view v >= 1 are the draw of view 0 -- stream 0, index 0, words 1 and
  * 2, the same scene id, the same formulas -- under the key (seed_lo + v * 0x9E3779B9, seed_hi + v * 0xBB67AE85), each sum
  * wrapping at 32 bits.  No other draw uses the view's key: the light's normals, the environment's gates and picks and everything

@@ -41,6 +41,9 @@ RENDER_SHADOW_RESET = 0x400
 RENDER_KEEP_HDR = 0x800
 OBJECT_STATS_CAPACITY = 1     # SLHIP_OBJECT_STATS_CAPACITY: status of slhip_render_object_stats when the word pool is too small
 OBJECT_MASKS_CAPACITY = 2     # SLHIP_OBJECT_MASKS_CAPACITY: status of slhip_render_object_masks when the word or the run pool is too small
+OBJECT_CROPS_CAPACITY = 3     # SLHIP_OBJECT_CROPS_CAPACITY: status of slhip_object_crops_select when d_crops is too small
+CROP_RGB, CROP_COORD, CROP_NORMALS, CROP_INSTANCE, CROP_MASK = 1, 2, 4, 8, 16      # SLHIP_CROP_*
+OBJECT_CROPS_MAX_SIZE = 1024
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
 COMM_ID_BYTES = 128
@@ -216,6 +219,27 @@ DEPTH_SENSOR_DTYPE = np.dtype([
 ])
 assert DEPTH_SENSOR_DTYPE.itemsize == 60
 
+# slhip_object_crop_params (include/slhip.h), 64 bytes
+OBJECT_CROP_PARAMS_DTYPE = np.dtype([
+    ("size", np.uint32), ("box", np.uint32), ("pad", np.float32), ("jitter_scale", np.float32), ("jitter_shift", np.float32),
+    ("min_px", np.uint32), ("min_visib_fract", np.float32), ("fx", np.float32), ("fy", np.float32), ("cx", np.float32),
+    ("cy", np.float32), ("seed_lo", np.uint32), ("seed_hi", np.uint32), ("scene_id_base", np.uint32), ("outputs", np.uint32),
+    ("isolate", np.uint32),
+])
+assert OBJECT_CROP_PARAMS_DTYPE.itemsize == 64
+# slhip_object_crop (include/slhip.h), 48 bytes: one window
+OBJECT_CROP_DTYPE = np.dtype([("scene", np.uint32), ("slot", np.uint32), ("x0", np.float32), ("y0", np.float32),
+                              ("side", np.float32), ("step", np.float32), ("K", np.float32, (4,)), ("_pad", np.uint32, (2,))])
+assert OBJECT_CROP_DTYPE.itemsize == 48
+
+
+class ObjectCropsOut(C.Structure):
+    """slhip_object_crops_out: the output pointers of slhip_object_crops_gather."""
+
+    _fields_ = [("d_rgb", C.c_void_p), ("d_coord", C.c_void_p), ("d_normals", C.c_void_p), ("d_instance", C.c_void_p),
+                ("d_mask", C.c_void_p)]
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -283,6 +307,7 @@ def view_key(seed_lo, seed_hi, view):
 
 
 SYNTH_STREAM_ENV = 4     # Philox stream of the environment draws (include/slhip.h, "Randomness")
+SYNTH_STREAM_CROP = 5    # Philox stream of the crop jitter (slhip_object_crops_select)
 SYNTH_SAMPLE_DISTINCT = 1
 SYNTH_RANDOM_PBR = 2
 SYNTH_SHADOWS = 4
@@ -377,6 +402,15 @@ def lib():
         L.slhip_depth_sensor_scratch_bytes.argtypes = [C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.slhip_depth_sensor.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "slhip_object_crops_select"):      # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_object_crops_check_params.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.slhip_object_crops_scratch_bytes.argtypes = [C.c_uint32, C.POINTER(C.c_uint64)]
+        L.slhip_object_crops_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+        L.slhip_object_crops_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RenderOut), C.c_uint32, C.c_int,
+                                                C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ObjectCropsOut), C.c_void_p]
+        L.slhip_object_crops_timing_enable.argtypes = [C.c_int]
+        L.slhip_object_crops_timings.argtypes = [C.POINTER(C.c_float * 2)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

@@ -424,6 +424,31 @@ class SceneBatch:
         for c in range(self.n_render_chunks()):
             yield self.render(c, mask, ssao, object_stats=object_stats, object_masks=object_masks)
 
+    def intrinsics(self):
+        """(fx, fy, cx, cy) of the batch's camera, read back from its projection (Scene.set_camera_intrinsics' convention)."""
+        P = self._proto._projection.astype(np.float64)
+        W, H = (float(v) for v in self.resolution)
+        return (P[0, 0] * W / 2.0, P[1, 1] * H / 2.0, (P[0, 2] + 1.0) * W / 2.0, (P[1, 2] + 1.0) * H / 2.0)
+
+    def crops(self, buffers, chunk=0, **kw):
+        """sl.object_crops.extract on the render of chunk `chunk` (`buffers` = what render(chunk, object_stats=True) or
+        render(chunk, object_masks=True) returned) with the batch's intrinsics, the scene ids of the chunk and the Philox key
+        of the view last placed -- every view of a pile gets its own jitter.  The result also carries `scene_global`
+        (= scene + chunk * render_chunk) and, when place(object_to_camera=True) keeps it, `object_to_camera` [n, 3, 4] of every
+        crop's object.  `kw`: the other arguments of extract (size, box, pad, jitter_scale, jitter_shift, ...)."""
+        from . import object_crops
+
+        for name in ("intrinsics", "seed", "scene_id_base"):
+            if name in kw:
+                raise TypeError("SceneBatch.crops sets `%s` itself" % name)
+        s0 = int(chunk) * self.render_chunk
+        key = _abi.view_key(int(self.params["seed_lo"]), int(self.params["seed_hi"]), self.view)
+        out = object_crops.extract(buffers, self.intrinsics(), seed=key, scene_id_base=int(self.params["scene_id_base"]) + s0, **kw)
+        out.scene_global = out.scene + s0
+        if self.object_to_camera is not None:
+            out.object_to_camera = self.object_to_camera[out.scene_global.long(), (out.slot - 1).long()]
+        return out
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

@@ -643,6 +643,8 @@ typedef struct {
     float post_kernel[25];  /* 5x5 weights of the post blur (sigma = 0.4)                          */
     float exposure_gain;    /* exp(deltaS), rounded to f32 (camera_model.py:130)                   */
     float noise_a, noise_b; /* signal-dependent variance factor, signal-independent std            */
+                            /* noise_a: 0 or >= 2^-24 -- the entry does not check it; below that the   */
+                            /* counts rgb / noise_a are no whole numbers in float32 any more          */
     float hue_shift;        /* -0.5 .. 0.5                                                         */
     uint32_t blur_enabled;  /* blur_sigma > 0                                                      */
     uint32_t noise_enabled; /* do_noise                                                            */

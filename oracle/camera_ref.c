@@ -7,7 +7,9 @@
  * oracle/ref_build/gen_camera_golden.py) for every deterministic stage; tests/test_oracle_camera.py
  * checks this file against them (to ~1e-6: torch's CPU conv2d / grid_sample do not document their
  * summation order).  The HIP path uses the same operation order as this file and is compared bit
- * for bit.  The noise stage is random (torch.poisson / normal_) and is pinned by moments only. */
+ * for bit.  The noise stage is random (torch.poisson / normal_) and is not restated here: its generator,
+ * stillleben_amd/csrc/slhip_rng.h, is restated by tests/sensor_rng_ref.py, and tests/test_gpu_sensor_rng.py
+ * compares every draw of the kernel with it, on top of the moments of tests/test_gpu_camera.py. */
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>

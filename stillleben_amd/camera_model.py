@@ -18,6 +18,9 @@ __all__ = ["chromatic_aberration", "blur", "exposure", "noise", "color_jitter", 
            "process_image", "process_batch"]
 
 
+MIN_NOISE_A = 2.0 ** -24      # the smallest noise_a above 0: 1 / noise_a * rgb must stay a whole number in float32
+
+
 def _gaussian(sigma):
     """5x5 kernel of the reference (camera_model.py:77-104), same float32 operation sequence."""
     ax = torch.arange(5).float()
@@ -31,7 +34,10 @@ def _gaussian(sigma):
 
 def make_params(chromatic_translation, chromatic_scaling, blur_sigma, exposure_deltaS, do_noise, noise_a, noise_b,
                 hue_shift, seed=None):
-    """One slhip_camera_params record (numpy) from the arguments of process_deterministic."""
+    """One slhip_camera_params record (numpy) from the arguments of process_deterministic.  With `do_noise` set, `noise_a` is 0 (no
+    Poisson part) or at least 2^-24: below that the counts 1 / noise_a * rgb are no longer whole numbers in float32."""
+    if do_noise and 0.0 < float(np.float32(noise_a)) < MIN_NOISE_A:
+        raise ValueError("noise_a = %g: 0, or at least 2^-24 (the Poisson counts are kept in float32)" % noise_a)
     p = np.zeros((), _abi.CAMERA_DTYPE)
     p["translation"] = torch.as_tensor(chromatic_translation, dtype=torch.float32).reshape(6).numpy()
     p["scaling"] = torch.as_tensor(chromatic_scaling, dtype=torch.float32).reshape(3).numpy()
@@ -82,14 +88,11 @@ def process_deterministic(rgb, chromatic_translation, chromatic_scaling, blur_si
     return process_batch(rgb.unsqueeze(0), [p])[0]
 
 
-@profiling.Timer("camera_model.process_image")
-def process_image(rgb):
-    """Process image with random noise parameters (camera_model.py:265-286)."""
-    assert rgb.dim() == 3
-    assert rgb.size(0) == 3
+def _random_parameters():
+    """The random arguments of process_image (camera_model.py:265-286), drawn in the reference's order.  A `noise_a` drawn
+    below MIN_NOISE_A (about one image in 670 000) counts as 0: at such a rate the Poisson part is the signal itself."""
     hue_jitter = 0.05
-    return process_deterministic(
-        rgb,
+    args = dict(
         chromatic_translation=torch.empty(3, 2).uniform_(-0.002, 0.002),
         chromatic_scaling=torch.empty(3).uniform_(0.998, 1.002),
         blur_sigma=random.uniform(0.0, 3.0) if random.random() > 0.3 else 0.0,
@@ -99,6 +102,17 @@ def process_image(rgb):
         noise_b=random.random() * 0.02,
         hue_shift=random.uniform(-hue_jitter, hue_jitter),
     )
+    if float(np.float32(args["noise_a"])) < MIN_NOISE_A:
+        args["noise_a"] = 0.0
+    return args
+
+
+@profiling.Timer("camera_model.process_image")
+def process_image(rgb):
+    """Process image with random noise parameters (camera_model.py:265-286)."""
+    assert rgb.dim() == 3
+    assert rgb.size(0) == 3
+    return process_deterministic(rgb, **_random_parameters())
 
 
 # ---- per-stage helpers of the reference API (PyTorch compositions, any device) ---------------------

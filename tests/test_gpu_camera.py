@@ -1,6 +1,6 @@
 """GPU parity tests of the camera model (slhip_camera_model through the C-ABI): bit-exact against the
 oracle (same operation order), within the documented float32 tolerances against the golden vectors of
-the REFERENCE's camera_model.py, noise stage by moments."""
+the REFERENCE's camera_model.py, noise stage by moments (draw by draw: tests/test_gpu_sensor_rng.py)."""
 import os
 
 import numpy as np

@@ -1,6 +1,7 @@
 """GPU tests of the depth sensor model (slhip_depth_sensor through sl.depth_sensor): flags and both outputs bit-exact against
 the NumPy restatement tests/depth_sensor_ref.py wherever the arithmetic is IEEE add, mul, div, floor and compare; the stages
-that go through the normal draws of the RNG (logf, cosf) by moments, as test_gpu_camera.py::test_noise_moments does."""
+that go through the normal draws of the RNG (logf, cosf) by moments here, and draw by draw against the restated generator
+(tests/sensor_rng_ref.py) in tests/test_gpu_sensor_rng.py."""
 import numpy as np
 import pytest
 import torch

@@ -45,7 +45,9 @@ extern "C" {
                                  5, additive (no struct or signature changed; detect with dlsym): slhip_object_stats,
                                     slhip_render_object_stats, slhip_render_object_stats_bytes; slhip_object_mask,
                                     slhip_render_object_masks, slhip_render_object_masks_bytes, slhip_object_masks_expand;
-                                    slhip_object_crops_check_params, _scratch_bytes, _select, _gather, _timing_enable, _timings */
+                                    slhip_object_crops_check_params, _scratch_bytes, _select, _gather, _timing_enable, _timings;
+                                    slhip_object_points_check_params, _scratch_bytes, _select, _gather, _host_pixels,
+                                    _timing_enable, _timings */
 #define SLHIP_NUM_LIGHTS 3 /* reference include/stillleben/common.h:17 */
 
 /* ---------------------------------------------------------------------------------------------
@@ -799,6 +801,107 @@ int slhip_object_crops_gather(const slhip_object_crop_params* params, const slhi
 int slhip_object_crops_timing_enable(int on);
 int slhip_object_crops_timings(float ms_out[2]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Object points: K pixels of every visible object of a render, drawn inside its visible mask, and
+ * what the render shows there -- the input of networks that take a fixed number of points per
+ * object (the "choose" indices, the camera-frame point cloud, the dense correspondence target).
+ * This project's addition, the reference has no counterpart.  Two steps on the device, as for the
+ * crops: slhip_object_points_select turns the statistics and mask records of a render into a
+ * compact list of point sets in ascending (scene, slot) order; slhip_object_points_gather finds
+ * the pixels in the kind-1 bit tiles of slhip_render_object_masks and gathers there, one workgroup
+ * per set.  The choice is integer arithmetic, the camera point float32 with one rounded IEEE
+ * operation at a time (no fma); tests/object_points_ref.py restates both in NumPy bit for bit.
+ * DESIGN.md "Object points" states the rules.
+ *
+ * Eligible: slot >= 1, px_visib >= min_px, (float)px_visib >= min_visib_fract * (float)px_all, and
+ * the slot has tiles (tile_box tx0 <= tx1).
+ * Tile order of a slot's visible pixels: the tiles of its box row-major, inside a tile the rising bit
+ * index of the kind-1 word (bit (y & 7) * 8 + (x & 7) = pixel (x, y)).  n = the set's n_visib
+ * (px_visib, the popcount of those words); the RANK of a visible pixel is its position in that order.
+ * Point j of K = n_points is a stratified draw, all integer (products in 64 bits):
+ *   lo = floor(j n / K), hi = floor((j + 1) n / K), width = hi - lo
+ *   rank = lo + (uint32_t)(((uint64_t)x_j * width) >> 32)                  (= lo when width == 0)
+ * with x_j word j & 3 of stream 6, index (slot << 12) | (j >> 2) ("Randomness" below); point j is the
+ * pixel of that rank.  Ranks rise with j and stay below n; for n >= K the K pixels are distinct and
+ * spread over the whole mask, for n <= K every visible pixel appears, for n == K point j is pixel j.
+ * When the words hold fewer than rank + 1 set bits (statistics and masks of different pictures), when
+ * the pixel lies outside the W x H picture or the tile box outside its tiles, or when the set's scene
+ * or slot lies outside [n_scenes][n_slots], every output of the point is zero and nothing is read
+ * out of bounds of the picture.
+ * The camera point of pixel (x, y): z = d_depth[((scene * H + y) * W + x) * depth_stride] as in
+ * slhip_depth_sensor (stride 4 on the w of d_coord, 1 on a dense plane such as the sensor's float
+ * output, whose holes are 0); valid iff z is finite and > 0; then
+ *   X = ((((float)x + 0.5f) - cx) * z) / fx,  Y likewise with y, cy, fy,  Z = z,  valid = 1.0f
+ * in the renderer's camera frame (OpenCV's: x right, y down, z forward); an invalid point is
+ * (0, 0, 0, 0).  Pixel j covers [j, j + 1), as for the crops: the rasteriser samples at j + 0.5.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_POINTS_PIXEL   1u   /* i16 [n,K,2] (x, y) */
+#define SLHIP_POINTS_CAMERA  2u   /* f32 [n,K,4] (X, Y, Z, valid) */
+#define SLHIP_POINTS_COORD   4u   /* f32 [n,K,4] d_coord at the pixel, bit for bit (object xyz, camera z) */
+#define SLHIP_POINTS_NORMALS 8u   /* f32 [n,K,4] d_normals at the pixel, bit for bit */
+#define SLHIP_POINTS_RGB     16u  /* u8  [n,K,4] d_rgb at the pixel */
+#define SLHIP_OBJECT_POINTS_MAX 16384
+#define SLHIP_OBJECT_POINTS_CAPACITY 4   /* status of slhip_object_points_select: d_sets is too small */
+
+typedef struct {
+    uint32_t n_points;         /* K, 1..SLHIP_OBJECT_POINTS_MAX                                              */
+    uint32_t min_px;           /* >= 1: fewer visible pixels -> no set                                       */
+    float min_visib_fract;     /* [0, 1]: a smaller visible share of the silhouette -> no set                */
+    float fx, fy, cx, cy;      /* intrinsics the picture was rendered with (Scene.set_camera_intrinsics)     */
+    uint32_t seed_lo, seed_hi; /* Philox key of the draw                                                     */
+    uint32_t scene_id_base;    /* scene id of scene 0 of d_stats                                            */
+    uint32_t outputs;          /* SLHIP_POINTS_* bits, at least one                                          */
+    uint32_t _pad;
+} slhip_object_point_params;   /* 48 bytes */
+
+typedef struct {
+    uint32_t scene, slot;
+    uint32_t n_visib;          /* px_visib of the slot when it was selected: the n of the rank rule         */
+    uint32_t _pad;
+} slhip_object_point_set;      /* 16 bytes */
+
+typedef struct {               /* outputs of slhip_object_points_gather; those not named in `outputs` are not touched */
+    int16_t* d_pixel;
+    float*   d_camera;
+    float*   d_coord;
+    float*   d_normals;
+    uint8_t* d_rgb;
+} slhip_object_points_out;
+
+/* Every rule of the parameter record against a W x H picture (sides 1..32768): 1 <= n_points <= SLHIP_OBJECT_POINTS_MAX, min_px >= 1,
+ * min_visib_fract in [0, 1], fx, fy > 0 and all four intrinsics finite, known output bits and at least one.  select and gather
+ * also refuse n_slots > 65536 (the slot shares the counter's index word with j >> 2).  A negative error with slhip_last_error
+ * text.  No device. */
+int slhip_object_points_check_params(const slhip_object_point_params* params, int W, int H);
+/* bytes of the d_scratch of slhip_object_points_select (8-byte aligned).  No device. */
+int slhip_object_points_scratch_bytes(uint32_t n_scenes, uint64_t* bytes);
+/* d_stats, d_masks: slhip_object_stats and slhip_object_mask [n_scenes][n_slots] (device) of one slhip_render_object_masks.
+ * Writes the records of all eligible (scene, slot) in ascending (scene, slot) order to d_sets (device, `capacity` records;
+ * n_scenes * (n_slots - 1) always suffices) and their number to *n_out (host).  Returns 0, SLHIP_OBJECT_POINTS_CAPACITY when
+ * the number exceeds `capacity` (*n_out is still the needed count; nothing is promised about d_sets), or a negative error.
+ * Synchronises `stream` once.                                                                                           */
+int slhip_object_points_select(const slhip_object_point_params* params, const slhip_object_stats* d_stats,
+                               const slhip_object_mask* d_masks, uint32_t n_scenes, uint32_t n_slots,
+                               slhip_object_point_set* d_sets, uint64_t capacity, void* d_scratch, uint64_t* n_out, void* stream);
+/* buffers: the render targets of the picture ([n_scenes,H,W,...]); only those a requested output reads must be non-NULL
+ * (d_coord, d_normals, d_rgb).  d_depth / depth_stride (in floats): the z plane of SLHIP_POINTS_CAMERA, required with that
+ * output only.  d_masks / d_words: the records and bit tiles of slhip_render_object_masks of the same picture, always
+ * required.  Null pointers and bad sizes are refused before anything touches the device; n_sets == 0 returns 0 without a
+ * launch.  Asynchronous on `stream`.                                                                                      */
+int slhip_object_points_gather(const slhip_object_point_params* params, const slhip_object_point_set* d_sets, uint64_t n_sets,
+                               const slhip_render_out* buffers, const float* d_depth, uint32_t depth_stride, uint32_t n_scenes,
+                               int W, int H, const slhip_object_mask* d_masks, const uint64_t* d_words, uint32_t n_slots,
+                               const slhip_object_points_out* out, void* stream);
+/* The pixels of ONE set on the host, by the same lookup (csrc/slhip_mask_select.h) on host words: tile_box and h_words are
+ * the slot's tile box and its kind-1 words (word 0 = the box's first tile); out_xy receives n_points pairs (x, y), (0, 0)
+ * where the words run out before the rank.  Host only, no device: the handle by which the lookup is tested without one.   */
+int slhip_object_points_host_pixels(const slhip_object_point_params* params, uint32_t scene, uint32_t slot, uint32_t n_visib,
+                                    const int32_t tile_box[4], const uint64_t* h_words, int16_t* out_xy);
+/* Developer hook (tools/time_object_points.py): with timing on, the two calls record HIP events around their kernels;
+ * slhip_object_points_timings waits for them and gives ms_out[0] = the last select, ms_out[1] = the last gather.   */
+int slhip_object_points_timing_enable(int on);
+int slhip_object_points_timings(float ms_out[2]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).
@@ -852,6 +955,8 @@ int slhip_stream_destroy(void* stream);
  * texture, x[1] picks it.  Gate: uniform(x) < p.  Pick: min(n - 1, (uint32_t)(uniform(x) * (float)n)), float32 throughout.
  * Stream 5, crop jitter (slhip_object_crops_select only; its key and scene id base are the caller's): index = the slot,
  * x[0] scales the window, x[1] and x[2] shift it along x and y.
+ * Stream 6, point ranks (slhip_object_points_gather only; its key and scene id base are the caller's): index =
+ * (slot << 12) | (j >> 2), x[j & 3] places point j inside its stratum of the visible pixels ("Object points" above).
  * Views (slhip_synth_place_view): azimuth and elevation of view v >= 1 are the draw of view 0 -- stream 0, index 0, words 1 and
  * 2, the same scene id, the same formulas -- under the key (seed_lo + v * 0x9E3779B9, seed_hi + v * 0xBB67AE85), each sum
  * wrapping at 32 bits.  No other draw uses the view's key: the light's normals, the environment's gates and picks and everything

@@ -28,13 +28,15 @@ from . import bop  # noqa: F401  (additive: BOP scene_camera / scene_gt entries 
 from . import depth_sensor  # noqa: F401  (additive: the depth channel's sensor model, the sibling of camera_model)
 from . import object_crops  # noqa: F401  (additive: per-object windows of a render for object-centric networks)
 from .object_crops import ObjectCrops  # noqa: F401
+from . import object_points  # noqa: F401  (additive: K pixels per visible object and the render's targets gathered there)
+from .object_points import ObjectPoints  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
     'Mesh', 'MeshCache', 'Object', 'Range3D', 'RenderPass', 'RenderPassResult', 'Scene', 'Texture',
     'Texture2D', 'Viewer', 'view', 'ManipulationSim', 'JobQueue', 'AssetTable', 'SceneBatch',
     'camera_model', 'diff', 'extension', 'losses', 'quat_to_matrix', 'matrix_to_quat', 'ObjectStats', 'ObjectMasks', 'EnvironmentBank',
-    'bop', 'depth_sensor', 'object_crops', 'ObjectCrops',
+    'bop', 'depth_sensor', 'object_crops', 'ObjectCrops', 'object_points', 'ObjectPoints',
 ]
 
 

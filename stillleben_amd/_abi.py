@@ -44,6 +44,9 @@ OBJECT_MASKS_CAPACITY = 2     # SLHIP_OBJECT_MASKS_CAPACITY: status of slhip_ren
 OBJECT_CROPS_CAPACITY = 3     # SLHIP_OBJECT_CROPS_CAPACITY: status of slhip_object_crops_select when d_crops is too small
 CROP_RGB, CROP_COORD, CROP_NORMALS, CROP_INSTANCE, CROP_MASK = 1, 2, 4, 8, 16      # SLHIP_CROP_*
 OBJECT_CROPS_MAX_SIZE = 1024
+OBJECT_POINTS_CAPACITY = 4    # SLHIP_OBJECT_POINTS_CAPACITY: status of slhip_object_points_select when d_sets is too small
+POINTS_PIXEL, POINTS_CAMERA, POINTS_COORD, POINTS_NORMALS, POINTS_RGB = 1, 2, 4, 8, 16      # SLHIP_POINTS_*
+OBJECT_POINTS_MAX = 16384
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
 COMM_ID_BYTES = 128
@@ -240,6 +243,25 @@ class ObjectCropsOut(C.Structure):
                 ("d_mask", C.c_void_p)]
 
 
+# slhip_object_point_params (include/slhip.h), 48 bytes
+OBJECT_POINT_PARAMS_DTYPE = np.dtype([
+    ("n_points", np.uint32), ("min_px", np.uint32), ("min_visib_fract", np.float32), ("fx", np.float32), ("fy", np.float32),
+    ("cx", np.float32), ("cy", np.float32), ("seed_lo", np.uint32), ("seed_hi", np.uint32), ("scene_id_base", np.uint32),
+    ("outputs", np.uint32), ("_pad", np.uint32),
+])
+assert OBJECT_POINT_PARAMS_DTYPE.itemsize == 48
+# slhip_object_point_set (include/slhip.h), 16 bytes: one set of points
+OBJECT_POINT_SET_DTYPE = np.dtype([("scene", np.uint32), ("slot", np.uint32), ("n_visib", np.uint32), ("_pad", np.uint32)])
+assert OBJECT_POINT_SET_DTYPE.itemsize == 16
+
+
+class ObjectPointsOut(C.Structure):
+    """slhip_object_points_out: the output pointers of slhip_object_points_gather."""
+
+    _fields_ = [("d_pixel", C.c_void_p), ("d_camera", C.c_void_p), ("d_coord", C.c_void_p), ("d_normals", C.c_void_p),
+                ("d_rgb", C.c_void_p)]
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -308,6 +330,7 @@ def view_key(seed_lo, seed_hi, view):
 
 SYNTH_STREAM_ENV = 4     # Philox stream of the environment draws (include/slhip.h, "Randomness")
 SYNTH_STREAM_CROP = 5    # Philox stream of the crop jitter (slhip_object_crops_select)
+SYNTH_STREAM_POINTS = 6  # Philox stream of the point ranks (slhip_object_points_gather)
 SYNTH_SAMPLE_DISTINCT = 1
 SYNTH_RANDOM_PBR = 2
 SYNTH_SHADOWS = 4
@@ -411,6 +434,18 @@ def lib():
                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ObjectCropsOut), C.c_void_p]
         L.slhip_object_crops_timing_enable.argtypes = [C.c_int]
         L.slhip_object_crops_timings.argtypes = [C.POINTER(C.c_float * 2)]
+    if hasattr(L, "slhip_object_points_select"):     # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_object_points_check_params.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.slhip_object_points_scratch_bytes.argtypes = [C.c_uint32, C.POINTER(C.c_uint64)]
+        L.slhip_object_points_select.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]
+        L.slhip_object_points_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RenderOut), C.c_void_p, C.c_uint32,
+                                                 C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                 C.POINTER(ObjectPointsOut), C.c_void_p]
+        L.slhip_object_points_host_pixels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]
+        L.slhip_object_points_timing_enable.argtypes = [C.c_int]
+        L.slhip_object_points_timings.argtypes = [C.POINTER(C.c_float * 2)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

@@ -4,7 +4,7 @@
 // same float32 operation order (IEEE add, mul, div, floor, compare under -ffp-contract=off), so records and windows are
 // bit-exact against it.
 //   k_crop_count   one wave per scene: the eligible slots, ballot + popcount over the slots in strides of 64
-//   k_crop_scan    one block: exclusive scan of the per-scene counts, the total behind them
+//   k_scan_counts  (slhip_scan.h) one block: exclusive scan of the per-scene counts, the total behind them
 //   k_crop_emit    the walk of k_crop_count again; every eligible lane writes its record at the scene's offset + its rank
 //   k_crop_gather  one thread per output pixel, 256 consecutive pixels of one crop per block: a pure streaming kernel
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "slhip.h"
 #include "slhip_common.h"
 #include "slhip_rng.h"
+#include "slhip_scan.h"
 
 namespace {
 
@@ -75,29 +76,6 @@ __global__ __launch_bounds__(256) void k_crop_count(Params p, const slhip_object
         n += (unsigned long long)__popcll(__ballot(ok));
     }
     if (lane == 0u) counts[scene] = n;
-}
-
-// counts[0 .. n) -> exclusive offsets in place, counts[n] = the total.  One block of 1024; n may exceed it (carry).
-__global__ __launch_bounds__(1024) void k_crop_scan(unsigned long long* __restrict__ counts, uint32_t n)
-{
-    __shared__ unsigned long long s[1024];
-    unsigned long long carry = 0ull;
-    for (uint32_t i0 = 0u; i0 < n; i0 += 1024u) {
-        const uint32_t i = i0 + threadIdx.x;
-        const unsigned long long v = i < n ? counts[i] : 0ull;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (uint32_t d = 1u; d < 1024u; d <<= 1) {
-            const unsigned long long add = threadIdx.x >= d ? s[threadIdx.x - d] : 0ull;
-            __syncthreads();
-            s[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < n) counts[i] = carry + s[threadIdx.x] - v;
-        carry += s[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0u) counts[n] = carry;
 }
 
 __global__ __launch_bounds__(256) void k_crop_emit(Params p, const slhip_object_stats* __restrict__ stats, uint32_t n_scenes,
@@ -338,7 +316,7 @@ extern "C" int slhip_object_crops_select(const slhip_object_crop_params* params,
     const uint32_t blocks = (n_scenes + 3u) / 4u;
     if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[0], stream));
     k_crop_count<<<blocks, 256, 0, stream>>>(*params, d_stats, n_scenes, n_slots, counts);
-    k_crop_scan<<<1, 1024, 0, stream>>>(counts, n_scenes);
+    slhip::k_scan_counts<1024><<<1, 1024, 0, stream>>>(counts, n_scenes);
     k_crop_emit<<<blocks, 256, 0, stream>>>(*params, d_stats, n_scenes, n_slots, counts, d_crops, capacity);
     SLHIP_LAUNCH_CHECK();
     if (g_timing) {

@@ -449,6 +449,25 @@ class SceneBatch:
             out.object_to_camera = self.object_to_camera[out.scene_global.long(), (out.slot - 1).long()]
         return out
 
+    def points(self, buffers, chunk=0, **kw):
+        """sl.object_points.extract on the render of chunk `chunk` (`buffers` = what render(chunk, object_masks=True) returned)
+        with the batch's intrinsics, the scene ids of the chunk and the Philox key of the view last placed -- every view of a
+        pile gets its own draw.  The result also carries `scene_global` (= scene + chunk * render_chunk) and, when
+        place(object_to_camera=True) keeps it, `object_to_camera` [n, 3, 4] of every set's object.  `kw`: the other arguments
+        of extract (n_points, min_px, min_visib_fract, outputs, depth)."""
+        from . import object_points
+
+        for name in ("intrinsics", "seed", "scene_id_base"):
+            if name in kw:
+                raise TypeError("SceneBatch.points sets `%s` itself" % name)
+        s0 = int(chunk) * self.render_chunk
+        key = _abi.view_key(int(self.params["seed_lo"]), int(self.params["seed_hi"]), self.view)
+        out = object_points.extract(buffers, self.intrinsics(), seed=key, scene_id_base=int(self.params["scene_id_base"]) + s0, **kw)
+        out.scene_global = out.scene + s0
+        if self.object_to_camera is not None:
+            out.object_to_camera = self.object_to_camera[out.scene_global.long(), (out.slot - 1).long()]
+        return out
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

@@ -47,6 +47,8 @@ extern "C" {
                                     slhip_render_object_masks, slhip_render_object_masks_bytes, slhip_object_masks_expand;
                                     slhip_object_crops_check_params, _scratch_bytes, _select, _gather, _timing_enable, _timings;
                                     slhip_object_points_check_params, _scratch_bytes, _select, _gather, _host_pixels,
+                                    _timing_enable, _timings;
+                                    slhip_object_keypoints_check_params, _fps_bytes, _fps, _fps_host, _project, _field,
                                     _timing_enable, _timings */
 #define SLHIP_NUM_LIGHTS 3 /* reference include/stillleben/common.h:17 */
 
@@ -902,6 +904,80 @@ int slhip_object_points_host_pixels(const slhip_object_point_params* params, uin
 int slhip_object_points_timing_enable(int on);
 int slhip_object_points_timings(float ms_out[2]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Object keypoints: the targets of keypoint-voting pose networks (PVN3D, FFB6D: per-point offsets to
+ * 3D keypoints of the object's class; PVNet: per-pixel vectors towards the projected keypoints), from
+ * what a batch keeps in HBM -- the mesh pool, object_to_camera of slhip_synth_place_view and the
+ * instance target.  This project's addition, the reference has no counterpart.  Three steps: a bank
+ * of keypoints per class by farthest point sampling (once per asset table), their projection per
+ * (scene, object), and the per-pixel field.  All float32, one rounded IEEE operation at a time (no
+ * fma), the parenthesisation below is the contract; csrc/slhip_keypoint_rules.h holds the rules for
+ * host and device, tests/object_keypoints_ref.py restates them in NumPy bit for bit.  DESIGN.md
+ * "Object keypoints".
+ *
+ * 1. FPS, per class.  Its vertices are d_pos[vtx_base .. vtx_base + n_verts), vtx_base that of
+ * d_templates[asset.draw_begin]; a class with draw_count == 0 or n_verts == 0 has none (nor one whose
+ * template or vertices lie outside the tables, or with more than max_verts vertices).
+ *   p_v = rows 0..2 of mesh_to_object applied to (x, y, z, 1), each ((m0*x + m1*y) + m2*z) + m3: the
+ *         object frame, the frame of the coord target
+ *   o = (bbox_min + bbox_max) * 0.5f per component
+ *   d2(a, b) = ((ax-bx)*(ax-bx) + (ay-by)*(ay-by)) + (az-bz)*(az-bz)
+ *   dmin[v] = d2(p_v, o); then for k = 0 .. n_fps-1:
+ *     i_k = the lowest v whose dmin[v] is the maximum (a scan upwards from -inf with a strict >: a NaN
+ *           never wins; when nothing wins, vertex 0),  kp_k = p_{i_k},
+ *     dmin[v] = d2(p_v, kp_k) < dmin[v] ? d2(p_v, kp_k) : dmin[v]
+ * With fewer distinct positions than n_fps the rule repeats the lowest index: that is the defined
+ * result.  With no vertices every keypoint is o and every index -1.
+ *
+ * 2. Projection, per (scene, object, k) with (x, y, z) = bank[object's asset][k] and r, t the rows of
+ * object_to_camera:  X = ((r00*x + r01*y) + r02*z) + t0, Y and Z likewise;
+ *   u = (fx * X) / Z + cx,  v = (fy * Y) / Z + cy      (pixel index x covers [x, x + 1), as for points and crops)
+ * Flags: SLHIP_KEYPOINT_IN_FRONT  X, Y, Z finite and Z > 0
+ *        SLHIP_KEYPOINT_INSIDE    in front, 0 <= u < W and 0 <= v < H
+ *        SLHIP_KEYPOINT_UNOCCLUDED  only with a depth plane: inside, the plane's z at pixel (floor(u), floor(v))
+ *                                 finite and > 0, and Z <= z + depth_tol
+ * Without IN_FRONT, u = v = 0 and the camera point is (0, 0, 0, 0); an asset >= n_assets gives all-zero outputs.
+ *
+ * 3. Field.  A pixel (x, y) with instance i, 1 <= i <= n_objects, belongs to object i - 1; for keypoint k
+ *   dx = u_k - ((float)x + 0.5f),  dy = v_k - ((float)y + 0.5f)
+ *   OFFSET: (dx, dy)      UNIT: l = sqrt(dx*dx + dy*dy), (dx / l, dy / l), (0, 0) when l == 0
+ * (sqrt and / correctly rounded), (0, 0) in both modes when the keypoint is not IN_FRONT.  Every other
+ * pixel (instance 0, negative, above n_objects) gets zeros in all 2 Kp floats.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_KEYPOINTS_MAX 32
+#define SLHIP_KEYPOINT_IN_FRONT   1u
+#define SLHIP_KEYPOINT_INSIDE     2u
+#define SLHIP_KEYPOINT_UNOCCLUDED 4u
+#define SLHIP_KEYPOINT_FIELD_OFFSET 0u
+#define SLHIP_KEYPOINT_FIELD_UNIT   1u
+
+typedef struct {
+    float fx, fy, cx, cy;      /* intrinsics the picture was rendered with; fx, fy > 0, all finite          */
+    int32_t W, H;              /* picture size, each side 1..32768                                           */
+    float depth_tol;           /* metres, finite and >= 0: how far behind the plane a keypoint still shows   */
+    uint32_t n_keypoints;      /* Kp, 1..SLHIP_KEYPOINTS_MAX                                                 */
+    uint32_t n_objects;        /* objects per scene, 1..SLHIP_SYNTH_MAX_OBJECTS                              */
+    uint32_t mode;             /* SLHIP_KEYPOINT_FIELD_* (slhip_object_keypoints_field only)                 */
+    uint32_t _pad[2];
+} slhip_object_keypoint_params; /* 48 bytes */
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_object_keypoints_check_params(const slhip_object_keypoint_params* params);
+/* bytes of the d_scratch of slhip_object_keypoints_fps: dmin, one row of max_verts floats per class.  No device. */
+int slhip_object_keypoints_fps_bytes(uint32_t n_assets, uint64_t max_verts, uint64_t* bytes);
+/* slhip_object_keypoints_fps, _fps_host and _project take records of the synthesis section and are declared there, below.
+ * d_instance i16 [n_scenes, H, W], d_uv and d_flags of the projection, scenes [first, first + count) of them into d_out f32
+ * [count, H, W, Kp, 2] (8-byte aligned): every float of the slice is written exactly once, nothing outside it.  A scene's
+ * field must stay below 2^31 (pixel, keypoint) pairs, count below 65536; a range past n_scenes, null pointers and bad
+ * parameters are refused before anything touches the device.  Asynchronous on `stream`.                                  */
+int slhip_object_keypoints_field(const slhip_object_keypoint_params* params, const int16_t* d_instance, const float* d_uv,
+                                 const uint8_t* d_flags, uint32_t n_scenes, uint32_t first, uint32_t count, float* d_out,
+                                 void* stream);
+/* Developer hook (tools/time_object_keypoints.py): with timing on, the three calls record HIP events around their kernels;
+ * slhip_object_keypoints_timings waits for them and gives the ms of the last fps, project and field (-1: not run).   */
+int slhip_object_keypoints_timing_enable(int on);
+int slhip_object_keypoints_timings(float ms_out[3]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).
@@ -1019,6 +1095,30 @@ typedef struct {
     float plane_pose[16];       /* Scene::backgroundPlanePose set by the tabletop set-up (scene.cpp:650-657) */
     float camera_pose[16];      /* out of slhip_synth_place: Scene::cameraPose                            */
 } slhip_synth_scene;
+
+/* Object keypoints ("Object keypoints" above), the entries that take the records of this section. */
+/* d_pos: float4 [n_vertices], the pool's positions; d_assets [n_assets] (1..SLHIP_SYNTH_MAX_ASSETS), d_templates
+ * [n_templates]; n_fps 1..SLHIP_KEYPOINTS_MAX; max_verts: the most vertices of a class (the row length of d_scratch).
+ * d_keypoints f32 [n_assets, n_fps, 4] = (x, y, z, 1), d_vertex i32 [n_assets, n_fps] = i_k.  One workgroup per class (this
+ * runs once per asset table).  Bad counts and null pointers are refused before anything touches the device.  Asynchronous
+ * on `stream`.                                                                                                            */
+int slhip_object_keypoints_fps(const float* d_pos, uint64_t n_vertices, const slhip_asset* d_assets, uint32_t n_assets,
+                               const slhip_draw* d_templates, uint32_t n_templates, uint32_t n_fps, uint64_t max_verts,
+                               void* d_scratch, float* d_keypoints, int32_t* d_vertex, void* stream);
+/* The same rule on host arrays through csrc/slhip_keypoint_rules.h (no row limit, no scratch).  A class whose template or
+ * vertices lie outside the tables has no vertices here too.  Host only, no device: the handle the CPU tests use.        */
+int slhip_object_keypoints_fps_host(const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets, uint32_t n_assets,
+                                    const slhip_draw* h_templates, uint32_t n_templates, uint32_t n_fps, float* h_keypoints,
+                                    int32_t* h_vertex);
+/* [n_scenes, n_objects, Kp] keypoints: d_bank f32 [n_assets, Kp, 4] (any bank, not only FPS), d_objects
+ * slhip_synth_object [n_scenes * n_objects] (only .asset is read), d_object_to_camera f32 [n_scenes, n_objects, 3, 4],
+ * d_depth / depth_stride as in slhip_object_points_gather, or NULL: no SLHIP_KEYPOINT_UNOCCLUDED.  Outputs: d_camera f32
+ * [.., 4] = (X, Y, Z, 1), d_uv f32 [.., 2], d_flags u8 [..].  Null pointers and bad sizes are refused before anything touches
+ * the device.  Asynchronous on `stream`.                                                                                  */
+int slhip_object_keypoints_project(const slhip_object_keypoint_params* params, const float* d_bank, uint32_t n_assets,
+                                   const slhip_synth_object* d_objects, const float* d_object_to_camera, uint32_t n_scenes,
+                                   const float* d_depth, uint32_t depth_stride, float* d_camera, float* d_uv, uint8_t* d_flags,
+                                   void* stream);
 
 /* Tabletop set-up of every scene of the batch (scene.cpp:612-678): d_bodies [n_scenes * n_objects],
  * d_settle_scenes [n_scenes] (has_plane = 1), d_objects [n_scenes * n_objects], d_scenes [n_scenes].

@@ -30,6 +30,8 @@ from . import object_crops  # noqa: F401  (additive: per-object windows of a ren
 from .object_crops import ObjectCrops  # noqa: F401
 from . import object_points  # noqa: F401  (additive: K pixels per visible object and the render's targets gathered there)
 from .object_points import ObjectPoints  # noqa: F401
+from . import object_keypoints  # noqa: F401  (additive: FPS keypoint banks, their projections and the per-pixel vector field)
+from .object_keypoints import KeypointBank, ObjectKeypoints  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -37,6 +39,7 @@ __all__ = [
     'Texture2D', 'Viewer', 'view', 'ManipulationSim', 'JobQueue', 'AssetTable', 'SceneBatch',
     'camera_model', 'diff', 'extension', 'losses', 'quat_to_matrix', 'matrix_to_quat', 'ObjectStats', 'ObjectMasks', 'EnvironmentBank',
     'bop', 'depth_sensor', 'object_crops', 'ObjectCrops', 'object_points', 'ObjectPoints',
+    'object_keypoints', 'KeypointBank', 'ObjectKeypoints',
 ]
 
 

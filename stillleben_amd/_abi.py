@@ -47,6 +47,9 @@ OBJECT_CROPS_MAX_SIZE = 1024
 OBJECT_POINTS_CAPACITY = 4    # SLHIP_OBJECT_POINTS_CAPACITY: status of slhip_object_points_select when d_sets is too small
 POINTS_PIXEL, POINTS_CAMERA, POINTS_COORD, POINTS_NORMALS, POINTS_RGB = 1, 2, 4, 8, 16      # SLHIP_POINTS_*
 OBJECT_POINTS_MAX = 16384
+KEYPOINTS_MAX = 32            # SLHIP_KEYPOINTS_MAX
+KEYPOINT_IN_FRONT, KEYPOINT_INSIDE, KEYPOINT_UNOCCLUDED = 1, 2, 4      # SLHIP_KEYPOINT_*: the flag bits of a projected keypoint
+KEYPOINT_FIELD_OFFSET, KEYPOINT_FIELD_UNIT = 0, 1                      # SLHIP_KEYPOINT_FIELD_*
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
 COMM_ID_BYTES = 128
@@ -262,6 +265,14 @@ class ObjectPointsOut(C.Structure):
                 ("d_rgb", C.c_void_p)]
 
 
+# slhip_object_keypoint_params (include/slhip.h), 48 bytes
+OBJECT_KEYPOINT_PARAMS_DTYPE = np.dtype([
+    ("fx", np.float32), ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("W", np.int32), ("H", np.int32),
+    ("depth_tol", np.float32), ("n_keypoints", np.uint32), ("n_objects", np.uint32), ("mode", np.uint32), ("_pad", np.uint32, (2,)),
+])
+assert OBJECT_KEYPOINT_PARAMS_DTYPE.itemsize == 48
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -446,6 +457,19 @@ def lib():
                                                       C.c_void_p]
         L.slhip_object_points_timing_enable.argtypes = [C.c_int]
         L.slhip_object_points_timings.argtypes = [C.POINTER(C.c_float * 2)]
+    if hasattr(L, "slhip_object_keypoints_field"):   # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_object_keypoints_check_params.argtypes = [C.c_void_p]
+        L.slhip_object_keypoints_fps_bytes.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.slhip_object_keypoints_fps.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_object_keypoints_fps_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                      C.c_uint32, C.c_void_p, C.c_void_p]
+        L.slhip_object_keypoints_project.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                     C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_object_keypoints_field.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32, C.c_void_p, C.c_void_p]
+        L.slhip_object_keypoints_timing_enable.argtypes = [C.c_int]
+        L.slhip_object_keypoints_timings.argtypes = [C.POINTER(C.c_float * 3)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

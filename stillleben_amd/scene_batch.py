@@ -251,6 +251,7 @@ class SceneBatch:
                 self.d_env_ids = torch.from_numpy(ids.copy()).to(dev)
             self.d_env_out = torch.full((self.n_scenes, 3), -1, dtype=torch.int32, device=dev)
         self.view, self.object_to_camera, self._view_keep = 0, None, None      # place(view=...)
+        self._object_to_camera_placed = False      # object_to_camera belongs to the view last placed (keypoints())
 
     # ---- camera (shared by all scenes of the batch; sl.Scene's setters) --------------------------------------
     def _set_projection(self):
@@ -381,6 +382,7 @@ class SceneBatch:
                                                   self._a(self.d_drec), self._a(self.d_crec), C.c_void_p(stream))
             _abi.check(st, "slhip_synth_place")
         self.view = int(view)
+        self._object_to_camera_placed = bool(object_to_camera)
 
     def views(self, n, mask=_abi.OUT_GT6, ssao=True, object_stats=False, object_to_camera=False, object_masks=False):
         """n pictures of every scene: places view v = 0 .. n - 1 in turn and yields (v, chunk, buffers) for every render chunk
@@ -466,6 +468,38 @@ class SceneBatch:
         out.scene_global = out.scene + s0
         if self.object_to_camera is not None:
             out.object_to_camera = self.object_to_camera[out.scene_global.long(), (out.slot - 1).long()]
+        return out
+
+    def keypoints(self, buffers, chunk=0, bank=None, depth=None, **kw):
+        """sl.object_keypoints.project for the render of chunk `chunk` (`buffers` = what render(chunk, ...) returned; only its
+        size is used) with the batch's intrinsics, its object records and the chunk's slice of `object_to_camera`: an
+        ObjectKeypoints whose scene b is scene b of the chunk.  `bank`: a KeypointBank of the batch's table
+        (sl.object_keypoints.bank(table, ...)) or a [A, Kp, 4] tensor.  `depth`: a float32 [B, H, W] plane, or True for the
+        ideal depth (the w of buffers.coord): enables the `unoccluded` flag.  `kw`: depth_tol.  Needs
+        place(object_to_camera=True) for the view last placed: the keypoints are projected with that camera."""
+        from . import object_keypoints
+
+        for name in ("intrinsics", "size", "object_to_camera", "objects"):
+            if name in kw:
+                raise TypeError("SceneBatch.keypoints sets `%s` itself" % name)
+        if bank is None:
+            raise TypeError("SceneBatch.keypoints needs a bank (sl.object_keypoints.bank(table, ...))")
+        if self.object_to_camera is None or not self._object_to_camera_placed:
+            raise RuntimeError("SceneBatch.keypoints needs object_to_camera of the view last placed: call "
+                               "place(object_to_camera=True) (the last place() did not keep it)")
+        rc = self.render_chunk
+        s0 = int(chunk) * rc
+        B = min(rc, self.n_scenes - s0)
+        if B <= 0:
+            raise IndexError("render chunk %d out of range" % chunk)
+        if depth is True:
+            depth = buffers.coord
+            if depth is None:
+                raise RuntimeError("object_keypoints: the `coord` target was not rendered, and depth=True reads it")
+        nb = self.n_objects * _abi.SYNTH_OBJECT_DTYPE.itemsize
+        out = object_keypoints.project(self.object_to_camera[s0:s0 + B], self.d_objects[s0 * nb:(s0 + B) * nb], bank,
+                                       self.intrinsics(), self.resolution, depth=depth, **kw)
+        out.scene0 = s0      # scene b of the result is scene s0 + b of the batch (offsets() pairs it with points.scene_global)
         return out
 
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------

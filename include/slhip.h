@@ -49,7 +49,9 @@ extern "C" {
                                     slhip_object_points_check_params, _scratch_bytes, _select, _gather, _host_pixels,
                                     _timing_enable, _timings;
                                     slhip_object_keypoints_check_params, _fps_bytes, _fps, _fps_host, _project, _field,
-                                    _timing_enable, _timings */
+                                    _timing_enable, _timings;
+                                    slhip_object_regions_check_params, _centres_bytes, _centres, _centres_host, _vertices,
+                                    _vertices_host, _label, _label_host, _timing_enable, _timings */
 #define SLHIP_NUM_LIGHTS 3 /* reference include/stillleben/common.h:17 */
 
 /* ---------------------------------------------------------------------------------------------
@@ -978,6 +980,81 @@ int slhip_object_keypoints_field(const slhip_object_keypoint_params* params, con
 int slhip_object_keypoints_timing_enable(int on);
 int slhip_object_keypoints_timings(float ms_out[3]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Object regions: the targets of pose networks that classify every pixel into a surface region of its
+ * object and regress inside it (GDR-Net's surface region attention, EPOS' surface fragments and
+ * fragment-local coordinates, SO-Pose, the coarse levels of ZebraPose).  This project's addition, the
+ * reference has no counterpart.  A bank of R region centres per class by the farthest point sampling
+ * of "Object keypoints" (once per asset table), the region of every mesh vertex with per-region counts
+ * and extents, and per pixel of a render the region of its object coordinate.  All float32, one
+ * rounded IEEE operation at a time (no fma); csrc/slhip_region_rules.h holds the rules for host and
+ * device, tests/object_regions_ref.py restates them in NumPy bit for bit.  DESIGN.md "Object regions".
+ *
+ * Nearest centre of a point p among the R centres c_0 .. c_{R-1} of a class, with d2 of "Object keypoints":
+ *   best = +inf, region = 0;  for r = 0 .. R-1 upwards:  d = d2(p, c_r);  if (d < best) { best = d; region = r; }
+ * A strict <: ties, duplicated centres included, go to the lowest index; a NaN distance never wins; when
+ * nothing wins (every d NaN or +inf) the region is 0.
+ *
+ * 1. Centres, per class: exactly the FPS of "Object keypoints" step 1 with n_fps = R, R in
+ * [1, SLHIP_REGIONS_MAX]: the first 32 centres are, bit for bit, the keypoint FPS.
+ *
+ * 2. Vertices.  Every vertex v of every class a (the ranges of step 1 of "Object keypoints", no row limit)
+ * gets r = nearest centre of p_v among the centres of a;  count[a][r] += 1;  with c = centre r of a
+ *   extent[a][r] = max over the region's vertices of (|p.x - c.x|, |p.y - c.y|, |p.z - c.z|, d2(p, c))
+ * each maximum taken on the bit patterns with the sign cleared (the order of non-negative floats; a NaN
+ * sorts above +inf), zeros for an empty region: integer maxima and sums, so the result does not depend
+ * on the order.  vertex_region[v] = r; SLHIP_REGION_NONE for a vertex of no class; a vertex inside the
+ * ranges of several classes carries the region of the highest such class (count and extent take it
+ * for every class).
+ *
+ * 3. Label, per pixel with instance i and coord (x, y, z, w; w is not read):  region = SLHIP_REGION_NONE
+ * when i < 1 or i > n_objects, when cls = classes[(image * n_objects + i - 1) * class_stride] is outside
+ * [0, n_assets), or when x, y or z is not finite; otherwise the nearest centre of (x, y, z) among the
+ * centres of cls.  local = (x - cx, y - cy, z - cz, d2((x, y, z), c)) of the winning centre c, zeros
+ * where region is NONE.  histogram[image][i - 1][region] counts the pixels that have a region.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_REGIONS_MAX 255
+#define SLHIP_REGION_NONE 255
+#define SLHIP_REGIONS_OUT_LOCAL     1u
+#define SLHIP_REGIONS_OUT_HISTOGRAM 2u
+
+typedef struct {
+    int32_t W, H;              /* picture size, each side 1..32768                                            */
+    uint32_t n_images;         /* N; N * H * W must stay below 2^32 - 2048 (split larger batches)             */
+    uint32_t n_objects;        /* O, objects per image, 1..SLHIP_SYNTH_MAX_OBJECTS                             */
+    uint32_t n_regions;        /* R, 1..SLHIP_REGIONS_MAX                                                      */
+    uint32_t n_assets;         /* A, classes of the bank, 1..SLHIP_SYNTH_MAX_ASSETS                            */
+    uint32_t outputs;          /* SLHIP_REGIONS_OUT_* bits; `region` is always written                         */
+    uint32_t _pad;
+} slhip_object_region_params; /* 32 bytes */
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_object_regions_check_params(const slhip_object_region_params* params);
+/* bytes of the d_scratch of slhip_object_regions_centres: one row of max_verts floats per class.  No device. */
+int slhip_object_regions_centres_bytes(uint32_t n_assets, uint64_t max_verts, uint64_t* bytes);
+/* slhip_object_regions_centres, _centres_host, _vertices and _vertices_host take records of the synthesis section and are
+ * declared there, below.
+ * Label: d_instance i16 [N, H, W]; d_coord f32 [N, H, W, 4] (16-byte aligned); d_classes i32, read at
+ * (image * O + object) * class_stride (1: a plain [N, O] tensor, 4: the asset of slhip_synth_object records in place);
+ * d_centres f32 [A, R, 4] (16-byte aligned).  d_region u8 [N, H, W], any alignment: every byte is written exactly once.
+ * d_local f32 [N, H, W, 4] (16-byte aligned) with SLHIP_REGIONS_OUT_LOCAL, d_histogram u32 [N, O, R] (4-byte aligned) with
+ * SLHIP_REGIONS_OUT_HISTOGRAM: the entry zeroes the histogram on `stream` before the kernel, the caller need not.  Without
+ * their bit the two pointers are not read.  An image whose pixels are all NONE never reads d_centres.  n_images == 0 does
+ * nothing; null pointers, misaligned buffers and bad parameters are refused before anything touches the device.
+ * Asynchronous on `stream`.                                                                                              */
+int slhip_object_regions_label(const slhip_object_region_params* params, const int16_t* d_instance, const float* d_coord,
+                               const int32_t* d_classes, uint32_t class_stride, const float* d_centres, uint8_t* d_region,
+                               float* d_local, uint32_t* d_histogram, void* stream);
+/* The same rules on host arrays through csrc/slhip_region_rules.h; h_histogram is zeroed first.  Host only, no device: the
+ * handle the CPU tests use.                                                                                              */
+int slhip_object_regions_label_host(const slhip_object_region_params* params, const int16_t* h_instance, const float* h_coord,
+                                    const int32_t* h_classes, uint32_t class_stride, const float* h_centres, uint8_t* h_region,
+                                    float* h_local, uint32_t* h_histogram);
+/* Developer hook (tools/time_object_regions.py): with timing on, the three device calls record HIP events around their
+ * work; slhip_object_regions_timings waits for them and gives the ms of the last centres, vertices and label (-1: not run). */
+int slhip_object_regions_timing_enable(int on);
+int slhip_object_regions_timings(float ms_out[3]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).
@@ -1119,6 +1196,29 @@ int slhip_object_keypoints_project(const slhip_object_keypoint_params* params, c
                                    const slhip_synth_object* d_objects, const float* d_object_to_camera, uint32_t n_scenes,
                                    const float* d_depth, uint32_t depth_stride, float* d_camera, float* d_uv, uint8_t* d_flags,
                                    void* stream);
+
+/* Object regions ("Object regions" above), the entries that take the records of this section. */
+/* The arguments of slhip_object_keypoints_fps with n_regions 1..SLHIP_REGIONS_MAX in place of n_fps (the same kernel, the
+ * same rule): d_centres f32 [n_assets, n_regions, 4] = (x, y, z, 1), d_vertex i32 [n_assets, n_regions].  Asynchronous on
+ * `stream`.                                                                                                               */
+int slhip_object_regions_centres(const float* d_pos, uint64_t n_vertices, const slhip_asset* d_assets, uint32_t n_assets,
+                                 const slhip_draw* d_templates, uint32_t n_templates, uint32_t n_regions, uint64_t max_verts,
+                                 void* d_scratch, float* d_centres, int32_t* d_vertex, void* stream);
+/* The same on host arrays (no row limit, no scratch).  Host only, no device. */
+int slhip_object_regions_centres_host(const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets, uint32_t n_assets,
+                                      const slhip_draw* h_templates, uint32_t n_templates, uint32_t n_regions, float* h_centres,
+                                      int32_t* h_vertex);
+/* Step 2: d_centres f32 [n_assets, n_regions, 4] (16-byte aligned; any bank, not only FPS) -> d_vertex_region u8 [n_vertices]
+ * (n_vertices below 2^32), d_count i32 [n_assets, n_regions], d_extent f32 [n_assets, n_regions, 4] (4-byte aligned).  The
+ * entry fills d_vertex_region with SLHIP_REGION_NONE and zeroes d_count and d_extent on `stream` before the kernel.  Bad
+ * counts and null pointers are refused before anything touches the device.  Asynchronous on `stream`.                     */
+int slhip_object_regions_vertices(const float* d_pos, uint64_t n_vertices, const slhip_asset* d_assets, uint32_t n_assets,
+                                  const slhip_draw* d_templates, uint32_t n_templates, const float* d_centres, uint32_t n_regions,
+                                  uint8_t* d_vertex_region, int32_t* d_count, float* d_extent, void* stream);
+/* The same on host arrays.  Host only, no device. */
+int slhip_object_regions_vertices_host(const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets, uint32_t n_assets,
+                                       const slhip_draw* h_templates, uint32_t n_templates, const float* h_centres,
+                                       uint32_t n_regions, uint8_t* h_vertex_region, int32_t* h_count, float* h_extent);
 
 /* Tabletop set-up of every scene of the batch (scene.cpp:612-678): d_bodies [n_scenes * n_objects],
  * d_settle_scenes [n_scenes] (has_plane = 1), d_objects [n_scenes * n_objects], d_scenes [n_scenes].

@@ -32,6 +32,8 @@ from . import object_points  # noqa: F401  (additive: K pixels per visible objec
 from .object_points import ObjectPoints  # noqa: F401
 from . import object_keypoints  # noqa: F401  (additive: FPS keypoint banks, their projections and the per-pixel vector field)
 from .object_keypoints import KeypointBank, ObjectKeypoints  # noqa: F401
+from . import object_regions  # noqa: F401  (additive: surface-region banks, per-vertex and per-pixel region labels)
+from .object_regions import RegionBank, ObjectRegions  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -39,7 +41,7 @@ __all__ = [
     'Texture2D', 'Viewer', 'view', 'ManipulationSim', 'JobQueue', 'AssetTable', 'SceneBatch',
     'camera_model', 'diff', 'extension', 'losses', 'quat_to_matrix', 'matrix_to_quat', 'ObjectStats', 'ObjectMasks', 'EnvironmentBank',
     'bop', 'depth_sensor', 'object_crops', 'ObjectCrops', 'object_points', 'ObjectPoints',
-    'object_keypoints', 'KeypointBank', 'ObjectKeypoints',
+    'object_keypoints', 'KeypointBank', 'ObjectKeypoints', 'object_regions', 'RegionBank', 'ObjectRegions',
 ]
 
 

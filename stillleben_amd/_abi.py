@@ -50,6 +50,8 @@ OBJECT_POINTS_MAX = 16384
 KEYPOINTS_MAX = 32            # SLHIP_KEYPOINTS_MAX
 KEYPOINT_IN_FRONT, KEYPOINT_INSIDE, KEYPOINT_UNOCCLUDED = 1, 2, 4      # SLHIP_KEYPOINT_*: the flag bits of a projected keypoint
 KEYPOINT_FIELD_OFFSET, KEYPOINT_FIELD_UNIT = 0, 1                      # SLHIP_KEYPOINT_FIELD_*
+REGIONS_MAX, REGION_NONE = 255, 255                                    # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
+REGIONS_OUT_LOCAL, REGIONS_OUT_HISTOGRAM = 1, 2                        # SLHIP_REGIONS_OUT_*
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
 COMM_ID_BYTES = 128
@@ -271,6 +273,12 @@ OBJECT_KEYPOINT_PARAMS_DTYPE = np.dtype([
     ("depth_tol", np.float32), ("n_keypoints", np.uint32), ("n_objects", np.uint32), ("mode", np.uint32), ("_pad", np.uint32, (2,)),
 ])
 assert OBJECT_KEYPOINT_PARAMS_DTYPE.itemsize == 48
+# slhip_object_region_params (include/slhip.h), 32 bytes
+OBJECT_REGION_PARAMS_DTYPE = np.dtype([
+    ("W", np.int32), ("H", np.int32), ("n_images", np.uint32), ("n_objects", np.uint32), ("n_regions", np.uint32),
+    ("n_assets", np.uint32), ("outputs", np.uint32), ("_pad", np.uint32),
+])
+assert OBJECT_REGION_PARAMS_DTYPE.itemsize == 32
 
 
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
@@ -470,6 +478,23 @@ def lib():
                                                    C.c_uint32, C.c_void_p, C.c_void_p]
         L.slhip_object_keypoints_timing_enable.argtypes = [C.c_int]
         L.slhip_object_keypoints_timings.argtypes = [C.POINTER(C.c_float * 3)]
+    if hasattr(L, "slhip_object_regions_label"):     # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_object_regions_check_params.argtypes = [C.c_void_p]
+        L.slhip_object_regions_centres_bytes.argtypes = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.slhip_object_regions_centres.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_object_regions_centres_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                        C.c_uint32, C.c_void_p, C.c_void_p]
+        L.slhip_object_regions_vertices.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                    C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_object_regions_vertices_host.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                         C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_object_regions_label.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_object_regions_label_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_object_regions_timing_enable.argtypes = [C.c_int]
+        L.slhip_object_regions_timings.argtypes = [C.POINTER(C.c_float * 3)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

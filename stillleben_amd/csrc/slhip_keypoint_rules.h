@@ -4,6 +4,9 @@
 // contract (include/slhip.h, "Object keypoints").
 #pragma once
 
+#include <stdint.h>
+
+#include "slhip.h"                // slhip_asset, slhip_draw
 #include "slhip_mask_walk.h"      // SLHIP_HD
 
 namespace slhip_kp {
@@ -23,6 +26,20 @@ SLHIP_HD P3 object_point(const float* mesh_to_object, float x, float y, float z)
     p.y = row_point(mesh_to_object + 4, x, y, z);
     p.z = row_point(mesh_to_object + 8, x, y, z);
     return p;
+}
+
+// The vertices of class a: [*base, *base + *n) of the pool, none when the class has no draw, its template or its vertices lie
+// outside the tables, or it has more vertices than the scratch row holds.
+SLHIP_HD void class_vertices(const slhip_asset& a, const slhip_draw* templates, uint32_t n_templates, uint64_t n_vertices,
+                             uint64_t max_verts, uint64_t* base, uint32_t* n)
+{
+    *base = 0u;
+    *n = 0u;
+    if (a.draw_count == 0u || a.n_verts == 0u || a.draw_begin >= n_templates) return;
+    const uint64_t b = templates[a.draw_begin].vtx_base;
+    if (b + a.n_verts > n_vertices || a.n_verts > max_verts) return;
+    *base = b;
+    *n = a.n_verts;
 }
 
 SLHIP_HD P3 bbox_centre(const float* bbox_min, const float* bbox_max)

@@ -36,19 +36,7 @@ constexpr uint32_t FIELD_TRIPS = 4u;        // units a lane of k_keypoints_field
 constexpr uint32_t MAX_KP = SLHIP_KEYPOINTS_MAX;
 constexpr uint32_t MAX_SLOTS = SLHIP_SYNTH_MAX_OBJECTS * MAX_KP;      // (object, keypoint) of one scene
 
-// The vertices of class a: [*base, *base + *n) of the pool, none when the class has no draw, its template or its vertices lie
-// outside the tables, or it has more vertices than the scratch row holds.
-__host__ __device__ inline void class_vertices(const slhip_asset& a, const slhip_draw* templates, uint32_t n_templates,
-                                               uint64_t n_vertices, uint64_t max_verts, uint64_t* base, uint32_t* n)
-{
-    *base = 0u;
-    *n = 0u;
-    if (a.draw_count == 0u || a.n_verts == 0u || a.draw_begin >= n_templates) return;
-    const uint64_t b = templates[a.draw_begin].vtx_base;
-    if (b + a.n_verts > n_vertices || a.n_verts > max_verts) return;
-    *base = b;
-    *n = a.n_verts;
-}
+using kp::class_vertices;
 
 __device__ __forceinline__ kp::Best wave_best(kp::Best b)
 {
@@ -246,14 +234,14 @@ bool g_timing = false;
 hipEvent_t g_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 bool g_timed[3] = {false, false, false};
 
-int check_fps(const char* who, uint32_t n_assets, uint32_t n_fps)
+int check_fps(const char* who, const char* what, uint32_t limit, uint32_t n_assets, uint32_t n_fps)
 {
     if (n_assets == 0u || n_assets > SLHIP_SYNTH_MAX_ASSETS) {
         slhip::set_error("%s: n_assets %u must be in [1, %u]", who, n_assets, SLHIP_SYNTH_MAX_ASSETS);
         return -1;
     }
-    if (n_fps < 1u || n_fps > MAX_KP) {
-        slhip::set_error("%s: n_fps %u must be in [1, %u]", who, n_fps, MAX_KP);
+    if (n_fps < 1u || n_fps > limit) {
+        slhip::set_error("%s: %s %u must be in [1, %u]", who, what, n_fps, limit);
         return -1;
     }
     return 0;
@@ -330,23 +318,37 @@ extern "C" int slhip_object_keypoints_fps_bytes(uint32_t n_assets, uint64_t max_
     return 0;
 }
 
+// The FPS of slhip_object_keypoints_fps for any count up to `limit` (slhip_object_regions_centres samples up to 255 centres by
+// the same kernel): checks, then the launch.  `what` names the count in the error text.
+int slhip::fps_device(const char* who, const char* what, uint32_t limit, const float* d_pos, uint64_t n_vertices,
+                      const slhip_asset* d_assets, uint32_t n_assets, const slhip_draw* d_templates, uint32_t n_templates,
+                      uint32_t n_fps, uint64_t max_verts, void* d_scratch, float* d_keypoints, int32_t* d_vertex, hipStream_t stream)
+{
+    if (const int st = check_fps(who, what, limit, n_assets, n_fps)) return st;
+    if (!d_assets || !d_keypoints || !d_vertex || (n_templates && !d_templates) || (n_vertices && !d_pos) ||
+        (max_verts && !d_scratch)) {
+        slhip::set_error("%s: null argument (assets, outputs, and templates / vertices / scratch unless their count is 0)", who);
+        return -1;
+    }
+    k_keypoints_fps<<<n_assets, FPS_BLOCK, 0, stream>>>(reinterpret_cast<const float4*>(d_pos), n_vertices, d_assets, d_templates,
+                                                       n_templates, n_fps, max_verts, (float*)d_scratch,
+                                                       reinterpret_cast<float4*>(d_keypoints), d_vertex);
+    SLHIP_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int slhip_object_keypoints_fps(const float* d_pos, uint64_t n_vertices, const slhip_asset* d_assets, uint32_t n_assets,
                                           const slhip_draw* d_templates, uint32_t n_templates, uint32_t n_fps, uint64_t max_verts,
                                           void* d_scratch, float* d_keypoints, int32_t* d_vertex, void* stream_)
 {
     static const char* who = "slhip_object_keypoints_fps";
     hipStream_t stream = (hipStream_t)stream_;
-    if (const int st = check_fps(who, n_assets, n_fps)) return st;
-    if (!d_assets || !d_keypoints || !d_vertex || (n_templates && !d_templates) || (n_vertices && !d_pos) ||
-        (max_verts && !d_scratch)) {
-        slhip::set_error("%s: null argument (assets, outputs, and templates / vertices / scratch unless their count is 0)", who);
-        return -1;
-    }
+    // (the checks come first: a refused call records no event)
+    if (const int st = check_fps(who, "n_fps", MAX_KP, n_assets, n_fps)) return st;
     if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[0], stream));
-    k_keypoints_fps<<<n_assets, FPS_BLOCK, 0, stream>>>(reinterpret_cast<const float4*>(d_pos), n_vertices, d_assets, d_templates,
-                                                       n_templates, n_fps, max_verts, (float*)d_scratch,
-                                                       reinterpret_cast<float4*>(d_keypoints), d_vertex);
-    SLHIP_LAUNCH_CHECK();
+    if (const int st = slhip::fps_device(who, "n_fps", MAX_KP, d_pos, n_vertices, d_assets, n_assets, d_templates, n_templates, n_fps,
+                                         max_verts, d_scratch, d_keypoints, d_vertex, stream))
+        return st;
     if (g_timing) {
         SLHIP_CHECK(hipEventRecord(g_ev[1], stream));
         g_timed[0] = true;
@@ -354,12 +356,11 @@ extern "C" int slhip_object_keypoints_fps(const float* d_pos, uint64_t n_vertice
     return 0;
 }
 
-extern "C" int slhip_object_keypoints_fps_host(const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets,
-                                               uint32_t n_assets, const slhip_draw* h_templates, uint32_t n_templates,
-                                               uint32_t n_fps, float* h_keypoints, int32_t* h_vertex)
+int slhip::fps_host(const char* who, const char* what, uint32_t limit, const float* h_pos, uint64_t n_vertices,
+                    const slhip_asset* h_assets, uint32_t n_assets, const slhip_draw* h_templates, uint32_t n_templates,
+                    uint32_t n_fps, float* h_keypoints, int32_t* h_vertex)
 {
-    static const char* who = "slhip_object_keypoints_fps_host";
-    if (const int st = check_fps(who, n_assets, n_fps)) return st;
+    if (const int st = check_fps(who, what, limit, n_assets, n_fps)) return st;
     if (!h_assets || !h_keypoints || !h_vertex || (n_templates && !h_templates) || (n_vertices && !h_pos)) {
         slhip::set_error("%s: null argument", who);
         return -1;
@@ -394,6 +395,14 @@ extern "C" int slhip_object_keypoints_fps_host(const float* h_pos, uint64_t n_ve
         }
     }
     return 0;
+}
+
+extern "C" int slhip_object_keypoints_fps_host(const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets,
+                                               uint32_t n_assets, const slhip_draw* h_templates, uint32_t n_templates,
+                                               uint32_t n_fps, float* h_keypoints, int32_t* h_vertex)
+{
+    return slhip::fps_host("slhip_object_keypoints_fps_host", "n_fps", MAX_KP, h_pos, n_vertices, h_assets, n_assets, h_templates,
+                           n_templates, n_fps, h_keypoints, h_vertex);
 }
 
 extern "C" int slhip_object_keypoints_project(const slhip_object_keypoint_params* params, const float* d_bank, uint32_t n_assets,

@@ -502,6 +502,29 @@ class SceneBatch:
         out.scene0 = s0      # scene b of the result is scene s0 + b of the batch (offsets() pairs it with points.scene_global)
         return out
 
+    def regions(self, buffers, chunk=0, bank=None, **kw):
+        """sl.object_regions.label for the render of chunk `chunk` (`buffers` = what render(chunk, ...) returned, with the
+        `instance` and `coord` targets) with the batch's object records, read in place: an ObjectRegions whose picture b is
+        scene b of the chunk.  `bank`: a RegionBank of the batch's table (sl.object_regions.bank(table, ...)) or a [A, R, 4]
+        tensor.  `kw`: local, histogram."""
+        from . import object_regions
+
+        for name in ("classes", "n_objects"):
+            if name in kw:
+                raise TypeError("SceneBatch.regions sets `%s` itself" % name)
+        if bank is None:
+            raise TypeError("SceneBatch.regions needs a bank (sl.object_regions.bank(table, ...))")
+        if buffers.instance is None or buffers.coord is None:
+            raise RuntimeError("object_regions: the `instance` and `coord` targets were not rendered")
+        rc = self.render_chunk
+        s0 = int(chunk) * rc
+        B = min(rc, self.n_scenes - s0)
+        if B <= 0 or int(buffers.instance.shape[0]) < B:
+            raise IndexError("render chunk %d out of range, or `buffers` holds fewer scenes than it" % chunk)
+        nb = self.n_objects * _abi.SYNTH_OBJECT_DTYPE.itemsize
+        return object_regions.label(buffers.instance[:B], buffers.coord[:B], self.d_objects[s0 * nb:(s0 + B) * nb], bank,
+                                    n_objects=self.n_objects, **kw)
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

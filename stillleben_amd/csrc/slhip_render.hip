@@ -26,6 +26,7 @@
 #include <type_traits>
 #include "slhip_common.h"
 #include "slhip_cubemap.h"
+#include "slhip_raster_walk.h"
 
 // Occupancy ceilings of the render kernels (waves per SIMD; 0 = whatever the registers allow; build-time experiment knobs).  In
 // the pipeline the settle stream is the critical path -- 2400 dependent launches whose single-wave blocks have to find a free
@@ -46,6 +47,13 @@
 #define SLHIP_LIGHT_KERNEL __attribute__((amdgpu_waves_per_eu(1, SLHIP_RENDER_WAVES)))
 #else
 #define SLHIP_LIGHT_KERNEL
+#endif
+// k_shadow_raster: at least six waves per SIMD (80 VGPRs; left alone it takes 84 and runs five -- its time follows its waves, see
+// k_raster); it fits without scratch
+#if SLHIP_RENDER_WAVES > 0
+#define SLHIP_SHADOW_RASTER_KERNEL SLHIP_LIGHT_KERNEL
+#else
+#define SLHIP_SHADOW_RASTER_KERNEL __attribute__((amdgpu_waves_per_eu(6)))
 #endif
 #if SLHIP_SSAO_WAVES > 0
 #define SLHIP_SSAO_KERNEL __attribute__((amdgpu_waves_per_eu(1, SLHIP_SSAO_WAVES)))
@@ -139,6 +147,7 @@ struct Setup {
     float z[3], invw[3];
     long long area2;  // > 0
     int flipped;      // original area2 < 0  (== front facing under FrontFace = CW)
+    int narrow;       // the edge functions fit 32 bits over the whole vertex extent (slhip_raster_walk.h)
     int bias[3];
     int xmin, xmax, ymin, ymax;
 };
@@ -180,6 +189,7 @@ __device__ __forceinline__ bool setup_finish(int W, int H, Setup& t)
     }
     int xmn = min(t.X[0], min(t.X[1], t.X[2])), xmx = max(t.X[0], max(t.X[1], t.X[2]));
     int ymn = min(t.Y[0], min(t.Y[1], t.Y[2])), ymx = max(t.Y[0], max(t.Y[1], t.Y[2]));
+    t.narrow = slhip_raster::narrow_ok((long long)xmx - xmn, (long long)ymx - ymn) ? 1 : 0;
     int x0 = (xmn - 128 + 255) >> 8, x1 = (xmx - 128) >> 8;
     int y0 = (ymn - 128 + 255) >> 8, y1 = (ymx - 128) >> 8;
     x0 = max(x0, 0); y0 = max(y0, 0);
@@ -239,6 +249,25 @@ __device__ __forceinline__ bool coverage(const Setup& t, int px, int py, float* 
     lambda[1] = (float)E[1] / fa;
     lambda[2] = (float)E[2] / fa;
     return true;
+}
+
+// coverage() for k_shadow_large, where a wave works on ONE triangle and t.narrow is wave-uniform: the same integers in
+// 32 bits where they fit (one v_cvt_f32_i32 per numerator instead of a software i64 -> f32), the same divisions, the same bits.
+// (px, py) lies inside the triangle's pixel box, hence inside its vertex extent.
+template <class I>
+__device__ __forceinline__ bool coverage_as(const Setup& t, int px, int py, float* lambda)
+{
+    I num[3];
+    if (!slhip_raster::cover<I>(t.X, t.Y, t.flipped, t.bias, px, py, num)) return false;
+    const float fa = (float)(I)t.area2;
+    lambda[0] = (float)num[0] / fa;
+    lambda[1] = (float)num[1] / fa;
+    lambda[2] = (float)num[2] / fa;
+    return true;
+}
+__device__ __forceinline__ bool coverage_walk(const Setup& t, int px, int py, float* lambda, int wide)
+{
+    return t.narrow && !wide ? coverage_as<int>(t, px, py, lambda) : coverage_as<long long>(t, px, py, lambda);
 }
 
 __device__ __forceinline__ unsigned depth24(float z)
@@ -722,9 +751,11 @@ struct ShadowTarget {
     unsigned* sm;  // [S,S] float bits
     int W;
     // per-chunk depth resolve in LDS (the north star's "LDS per-tile bins"): fragments inside the block's window take an LDS
-    // atomic; the window is written to the map once, row by row (k_shadow_raster).  win == nullptr: no window (k_shadow_large)
+    // atomic; the window is written to the map once, row by row (k_shadow_raster).  Only wnx x wny texels from (wx0, wy0) are
+    // cleared and flushed: a fragment outside them goes to the map itself.  wnx == 0: no window (k_shadow_large)
     unsigned* win;
     int wx0, wy0;
+    unsigned wnx, wny;
     __device__ __forceinline__ void emit(const Setup& t, int px, int py, const float* l) const
     {
         const float z = interp(l, t.z[0], t.z[1], t.z[2]);
@@ -732,7 +763,7 @@ struct ShadowTarget {
         const unsigned bits = __float_as_uint(z);  // z >= 0: uint order == float order
 #if SLHIP_SHADOW_WINDOW
         const unsigned ux = (unsigned)(px - wx0), uy = (unsigned)(py - wy0);
-        if (win != nullptr && ux < (unsigned)SLHIP_SHADOW_WINDOW && uy < (unsigned)SLHIP_SHADOW_WINDOW) {
+        if (ux < wnx && uy < wny) {
             atomicMin(win + uy * SLHIP_SHADOW_WINDOW_PITCH + ux, bits);
             return;
         }
@@ -754,54 +785,66 @@ struct QItem {
 
 // All pixels of the triangle's bounding box by one thread.  The edge functions are exact integers,
 // so walking them incrementally (E(px+1) = E(px) - 256 dY, E(py+1) = E(py) + 256 dX) gives the very
-// values coverage() computes from scratch -- at three 64-bit adds per pixel instead of six 64-bit
+// values coverage() computes from scratch -- at three adds per pixel instead of six 64-bit
 // multiplies.  The top-left bias is folded in: a pixel is covered iff all three biased values are
-// >= 0, i.e. iff the sign bit of their OR is clear.
-template <class Target>
-__device__ __forceinline__ void raster_bbox(const Setup& t, const Target& tgt)
+// >= 0, i.e. iff the sign bit of their OR is clear.  I: the integer the walk is carried in (slhip_raster_walk.h).
+template <class I, class Target>
+__device__ __forceinline__ void raster_bbox_as(const Setup& t, const Target& tgt)
 {
-    const int cx = 256 * t.xmin + 128, cy = 256 * t.ymin + 128;   // 32-bit factors, see coverage()
-    long long row[3], sx[3], sy[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int a = (i + 1) % 3, b = (i + 2) % 3;
-        const int Ai = t.X[b] - t.X[a], Bi = t.Y[b] - t.Y[a];
-        long long e = (long long)Ai * (long long)(cy - t.Y[a]) - (long long)Bi * (long long)(cx - t.X[a]);
-        long long dx = -256ll * (long long)Bi, dy = 256ll * (long long)Ai;
-        if (t.flipped) { e = -e; dx = -dx; dy = -dy; }
-        row[i] = e + t.bias[i]; sx[i] = dx; sy[i] = dy;
-    }
-    const float fa = (float)t.area2;
+    slhip_raster::Walk<I> w;
+    w.start(t.X, t.Y, t.flipped, t.bias, t.xmin, t.ymin);
+    const float fa = (float)(I)t.area2;
     // ONE flat loop over the box: the lanes of a wave hold boxes of different shapes, and a nested
     // loop would run (max height) x (max width) iterations instead of (max area)
     const int bw = t.xmax - t.xmin + 1, n = bw * (t.ymax - t.ymin + 1);
-    long long e0 = row[0], e1 = row[1], e2 = row[2];
     int px = t.xmin, py = t.ymin;
     for (int k = 0; k < n; ++k) {
-        if ((e0 | e1 | e2) >= 0) {
+        if (w.inside()) {
             float l[3];
-            l[0] = (float)(e0 - t.bias[0]) / fa;
-            l[1] = (float)(e1 - t.bias[1]) / fa;
-            l[2] = (float)(e2 - t.bias[2]) / fa;
+            l[0] = (float)w.numerator(0) / fa;
+            l[1] = (float)w.numerator(1) / fa;
+            l[2] = (float)w.numerator(2) / fa;
             tgt.emit(t, px, py, l);
         }
         if (px == t.xmax) {
             px = t.xmin; ++py;
-            row[0] += sy[0]; row[1] += sy[1]; row[2] += sy[2];
-            e0 = row[0]; e1 = row[1]; e2 = row[2];
+            w.next_row();
         } else {
             ++px;
-            e0 += sx[0]; e1 += sx[1]; e2 += sx[2];
+            w.step_x();
+        }
+    }
+}
+
+// The 32-bit walk when every lane of the wave that walks a box qualifies (the usual case: an in-place box has at most
+// kSmallArea texels and its triangle is rarely larger), else the 64-bit values for the whole wave: one loop per wave, never
+// both.  The 64-bit form evaluates every texel from scratch (coverage_as: the same integers the walk would reach) instead of
+// walking: it keeps no walk state, so the kernels' register count is the narrow walk's.  With BOTH walks in the kernel,
+// k_raster<false> took 85 VGPRs instead of 70 and k_shadow_raster 86 instead of 78 (5 waves per SIMD instead of 7 and 6), and the
+// isolated phases of 1024 C2 scenes went from 4.13 to 4.56 ms and from 11.01 to 11.25 ms (profiles/r08).
+template <class Target>
+__device__ __forceinline__ void raster_bbox(const Setup& t, const Target& tgt, int wide)
+{
+    if (!wide && __all(t.narrow)) {
+        raster_bbox_as<int>(t, tgt);
+    } else {
+        const int bw = t.xmax - t.xmin + 1, n = bw * (t.ymax - t.ymin + 1);
+        int px = t.xmin, py = t.ymin;
+        for (int k = 0; k < n; ++k) {
+            float l[3];
+            if (coverage_as<long long>(t, px, py, l)) tgt.emit(t, px, py, l);
+            if (px == t.xmax) { px = t.xmin; ++py; } else ++px;
         }
     }
 }
 
 // Rasterise one sub-triangle: small ones in place, larger ones to the queue (or in place if
-// the queue is full).
+// the queue is full).  wide: the 64-bit values whatever the triangle (SLHIP_RASTER_WIDE, which slhip_render passes down; the
+// silhouette pass of slhip_render_stats.inc has no such knob and walks narrow where it can).
 template <class Target>
 __device__ __forceinline__ void raster_or_enqueue(const Setup& t, const Target& tgt, unsigned* queue,
                                                   unsigned capacity, unsigned draw, unsigned tri_sub,
-                                                  unsigned scene_aux, int small_area)
+                                                  unsigned scene_aux, int small_area, int wide = 0)
 {
     const int bw = t.xmax - t.xmin + 1, bh = t.ymax - t.ymin + 1;
     bool in_place = bw * bh <= small_area;
@@ -831,7 +874,7 @@ __device__ __forceinline__ void raster_or_enqueue(const Setup& t, const Target& 
             in_place = true;
         }
     }
-    if (in_place) raster_bbox(t, tgt);
+    if (in_place) raster_bbox(t, tgt, wide);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -851,7 +894,7 @@ __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_po
                                              const float* __restrict__ depth_peel,
                                              unsigned long long* __restrict__ vis, unsigned* queue,
                                              unsigned capacity, const float4* __restrict__ clipbuf,
-                                             const uint4* __restrict__ screen, int small_area)
+                                             const uint4* __restrict__ screen, int small_area, int wide)
 {
     const slhip_chunk ch = chunks[chunk];
     if (threadIdx.x >= ch.count) return;
@@ -876,7 +919,7 @@ __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_po
         const uint4 s0 = screen[dr->clip_base + vi[0]], s1 = screen[dr->clip_base + vi[1]], s2 = screen[dr->clip_base + vi[2]];
         if (screen_all_inside(s0, s1, s2)) {     // clip_near() would hand the triangle through
             Setup t;
-            if (setup_from_screen(s0, s1, s2, W, H, t)) raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri, ch.scene, small_area);
+            if (setup_from_screen(s0, s1, s2, W, H, t)) raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri, ch.scene, small_area, wide);
             return;
         }
         ClipVert cv[3];
@@ -893,7 +936,7 @@ __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_po
             if (sub >= n - 2) break;
             Setup t;
             if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
-            raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri | ((unsigned)sub << 31), ch.scene, small_area);
+            raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri | ((unsigned)sub << 31), ch.scene, small_area, wide);
         }
     } else {
         ClipVert cv[3];
@@ -954,7 +997,8 @@ __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_po
 
 // The grid strides over the chunk list: the plain instantiation is launched with one block per chunk, the discard-testing one
 // with a few thousand blocks that skim the list for the (usually few or no) chunks that are theirs -- 340 k blocks that look at
-// one chunk header each and leave cost 1.1 ms per 1024 C2 scenes.
+// one chunk header each and leave cost 1.1 ms per 1024 C2 scenes when that was measured; a C2 scene has about 1 200 chunks
+// (1.2 M per 1024 scenes, profiles/r08/raster_box_stats.txt), so one block per chunk would cost more than that today.
 template <bool kAttr>
 __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_raster(slhip_mesh_pool pool, const slhip_scene* __restrict__ scenes,
                                                 const slhip_draw* __restrict__ draws,
@@ -962,10 +1006,10 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_raster(slhip_mesh_po
                                                 const float* __restrict__ depth_peel,
                                                 unsigned long long* __restrict__ vis, unsigned* queue,
                                                 unsigned capacity, const float4* __restrict__ clipbuf,
-                                                const uint4* __restrict__ screen, int small_area)
+                                                const uint4* __restrict__ screen, int small_area, int wide)
 {
     for (unsigned c = blockIdx.x; c < n_chunks; c += gridDim.x)
-        raster_chunk<kAttr>(c, pool, scenes, draws, chunks, W, H, depth_peel, vis, queue, capacity, clipbuf, screen, small_area);
+        raster_chunk<kAttr>(c, pool, scenes, draws, chunks, W, H, depth_peel, vis, queue, capacity, clipbuf, screen, small_area, wide);
 }
 
 // k_large: one wave per (triangle, 8x8 tile); lane == pixel.  Every wave takes a CONTIGUOUS run of
@@ -1023,6 +1067,8 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_large(slhip_mesh_poo
         const int py = (int)((it.tile >> 16) << 3) + (int)(lane >> 3);
         if (px < t.xmin || px > t.xmax || py < t.ymin || py > t.ymax) continue;
         float l[3];
+        // (the 64-bit coverage: what is queued here is the plane's two triangles and little else, and they never fit the narrow
+        // form -- with the choice in the loop the phase went from 2.55 to 2.66 ms per 1024 C2 scenes, profiles/r08)
         if (!coverage(t, px, py, l)) continue;
         MainTarget tgt;
         tgt.vis = vis + (size_t)it.scene_aux * W * H;
@@ -1057,18 +1103,38 @@ __device__ __forceinline__ void shadow_clip(const slhip_mesh_pool& pool, const f
 // k_shadow_large resolves for the large ones), and after the shading pass k_shadow_restore resets exactly those tiles.  The
 // per-call clear of the whole 2048^2 map (16.8 MB per scene and light, more than the whole G-buffer of the scene) is gone;
 // what is written back is proportional to what was drawn.
+// Minimum (kMax: maximum) of v over the 64 lanes of a wave, in registers: a scan of every row of 16 lanes (row_shr 1, 2, 4, 8), the
+// last lane of rows 0 / 2 into rows 1 / 3 (row_bcast 15), lane 31 into rows 2 and 3 (row_bcast 31) -- lane 63 then holds the
+// wave's value.  All 64 lanes must be active.  (256 lanes meeting in ONE LDS word with atomicMin, as the window origin was found
+// before, serialise lane by lane: the four such atomics of the sized window alone cost more than the clear and flush they saved,
+// profiles/r08.)
+template <bool kMax>
+__device__ __forceinline__ int wave_minmax(int v)
+{
+    constexpr int ident = kMax ? (int)0x80000000 : 0x7fffffff;
+#define SLHIP_DPP_STEP(ctrl, rows)                                                       \
+    {                                                                                    \
+        const int o = __builtin_amdgcn_update_dpp(ident, v, ctrl, rows, 0xf, false);     \
+        v = kMax ? max(v, o) : min(v, o);                                                \
+    }
+    SLHIP_DPP_STEP(0x111, 0xf) SLHIP_DPP_STEP(0x112, 0xf) SLHIP_DPP_STEP(0x114, 0xf) SLHIP_DPP_STEP(0x118, 0xf)
+    SLHIP_DPP_STEP(0x142, 0xa) SLHIP_DPP_STEP(0x143, 0xc)
+#undef SLHIP_DPP_STEP
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
 constexpr int kShadowTile = 64;
 constexpr int kShadowMaxWords = 32;   // LDS bitmap of k_shadow_raster: 1024 tiles = a 2048^2 map
 __host__ __device__ inline int shadow_tiles_x(int S) { return (S + kShadowTile - 1) / kShadowTile; }
 __host__ __device__ inline int shadow_tile_words(int S) { return (shadow_tiles_x(S) * shadow_tiles_x(S) + 31) / 32; }
 
-__global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_shadow_raster(slhip_mesh_pool pool, const slhip_scene* __restrict__ scenes,
+__global__ __launch_bounds__(256) SLHIP_SHADOW_RASTER_KERNEL void k_shadow_raster(slhip_mesh_pool pool, const slhip_scene* __restrict__ scenes,
                                                        const slhip_draw* __restrict__ draws,
                                                        const slhip_chunk* __restrict__ chunks, int S,
                                                        unsigned* __restrict__ shadow, unsigned* queue,
                                                        unsigned capacity, const float4* __restrict__ clipbuf,
                                                        unsigned n_clip_verts, unsigned* __restrict__ tile_bits, int nl,
-                                                       int small_area)
+                                                       int small_area, int wide)
 {
     __shared__ unsigned bm[SLHIP_NUM_LIGHTS][kShadowMaxWords];   // the chunk's touched tiles, ORed into the scene's bits at the end
     const slhip_chunk ch = chunks[blockIdx.x];
@@ -1078,6 +1144,11 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_shadow_raster(slhip_
     if (!(dr->flags & SLHIP_DRAW_CASTS_SHADOW)) return;      // block-uniform
     const int tx_n = shadow_tiles_x(S), words = shadow_tile_words(S);
     for (int k = (int)threadIdx.x; k < SLHIP_NUM_LIGHTS * kShadowMaxWords; k += 256) bm[k / kShadowMaxWords][k % kShadowMaxWords] = 0u;
+#if SLHIP_SHADOW_WINDOW
+    // per light and wave: min x, min y, max x, max y of the pixel boxes the wave walks in place (a slot per light: a light for which
+    // the chunk walks nothing costs one barrier and no more, and no wave overwrites what another still reads)
+    __shared__ int4 wbox[SLHIP_NUM_LIGHTS][4];
+#endif
     __syncthreads();
     const bool have_tri = threadIdx.x < ch.count;
     const unsigned tri = ch.first_tri + (have_tri ? threadIdx.x : 0u);
@@ -1087,11 +1158,13 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_shadow_raster(slhip_
     // The chunk's triangles are neighbours on the mesh: most of their fragments fall into one small patch of the map.  A
     // SLHIP_SHADOW_WINDOW^2-texel window of LDS is placed at the corner of the chunk's pixel boxes; fragments inside it are
     // resolved there (LDS atomics), and the touched texels go to the map once, 64 consecutive texels per atomic instruction --
-    // the same minimum per texel, whatever the order.
+    // the same minimum per texel, whatever the order.  The chunk first finds the union of the boxes it will walk (wave_minmax):
+    // a chunk that walks nothing for this light (all of it facing the light, or queued) clears and scans nothing, the others only
+    // the rows and columns of (union box n window) -- the columns rounded up to a power of two, so that a texel's index stays
+    // shift and mask.  Fragments outside that rectangle take the map's own atomic, as those outside the window always did.
     constexpr int kWin = SLHIP_SHADOW_WINDOW;
     constexpr int kPitch = SLHIP_SHADOW_WINDOW_PITCH;
     __shared__ unsigned win[kWin * kPitch];
-    __shared__ int worg[2];
 #endif
     // one block per chunk, the (few) active lights in a loop: the index fetch is shared and no
     // workgroups are launched for lights that are off
@@ -1103,12 +1176,28 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_shadow_raster(slhip_
         bool draw = have_tri && setup_from_screen(sp[i0], sp[i1], sp[i2], S, S, t);
         if (draw && t.flipped) draw = false;  // front face culled
 #if SLHIP_SHADOW_WINDOW
-        if (threadIdx.x < 2) worg[threadIdx.x] = 0x7fffffff;
-        for (int k = (int)threadIdx.x; k < kWin * kPitch; k += 256) win[k] = 0x3F800000u;      // 1.0: the cleared map
+        // the triangles raster_or_enqueue() walks in place (if the queue is full it walks a larger one too: that one's fragments
+        // fall outside the rectangle below and go to the map)
+        {
+            const bool walks = draw && (t.xmax - t.xmin + 1) * (t.ymax - t.ymin + 1) <= small_area;
+            const int bx0 = wave_minmax<false>(walks ? t.xmin : 0x7fffffff), by0 = wave_minmax<false>(walks ? t.ymin : 0x7fffffff);
+            const int bx1 = wave_minmax<true>(walks ? t.xmax : -1), by1 = wave_minmax<true>(walks ? t.ymax : -1);
+            if ((threadIdx.x & 63u) == 0u) wbox[light][threadIdx.x >> 6] = make_int4(bx0, by0, bx1, by1);
+        }
         __syncthreads();
-        if (draw) { atomicMin(&worg[0], t.xmin); atomicMin(&worg[1], t.ymin); }
-        __syncthreads();
-        const int wx0 = worg[0], wy0 = worg[1];
+        const int4 b0 = wbox[light][0], b1 = wbox[light][1], b2 = wbox[light][2], b3 = wbox[light][3];
+        const int wx0 = min(min(b0.x, b1.x), min(b2.x, b3.x)), wy0 = min(min(b0.y, b1.y), min(b2.y, b3.y));
+        const bool have_win = wx0 != 0x7fffffff;      // block-uniform
+        unsigned wnx = 0u, wny = 0u, wsh = 0u;
+        if (have_win) {
+            // 1 .. kWin (clamped from below as well: the clear and the flush index LDS by them)
+            wnx = (unsigned)max(min(max(max(b0.z, b1.z), max(b2.z, b3.z)) - wx0 + 1, kWin), 1);
+            wny = (unsigned)max(min(max(max(b0.w, b1.w), max(b2.w, b3.w)) - wy0 + 1, kWin), 1);
+            wsh = 32u - (unsigned)__clz((int)wnx - 1);               // columns cleared and scanned: 1 << wsh >= wnx, <= kWin
+            const unsigned n = wny << wsh, cmask = (1u << wsh) - 1u;
+            for (unsigned k = threadIdx.x; k < n; k += 256) win[(k >> wsh) * kPitch + (k & cmask)] = 0x3F800000u;   // 1.0: the cleared map
+            __syncthreads();
+        }
 #endif
         if (draw) {
             // tiles of the triangle's pixel box (a 16k-triangle object: almost always one tile, at most a handful)
@@ -1124,23 +1213,24 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_shadow_raster(slhip_
             tgt.sm = shadow + ((size_t)ch.scene * nl + light) * S * S;
             tgt.W = S;
 #if SLHIP_SHADOW_WINDOW
-            tgt.win = win; tgt.wx0 = wx0; tgt.wy0 = wy0;
+            tgt.win = win; tgt.wx0 = wx0; tgt.wy0 = wy0; tgt.wnx = wnx; tgt.wny = wny;
 #else
-            tgt.win = nullptr; tgt.wx0 = 0; tgt.wy0 = 0;
+            tgt.win = nullptr; tgt.wx0 = 0; tgt.wy0 = 0; tgt.wnx = 0u; tgt.wny = 0u;
 #endif
-            raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri, ch.scene | ((unsigned)light << 24), small_area);
+            raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri, ch.scene | ((unsigned)light << 24), small_area, wide);
         }
 #if SLHIP_SHADOW_WINDOW
-        __syncthreads();
-        if (wx0 != 0x7fffffff) {
+        if (have_win) {
+            __syncthreads();
             unsigned* sm = shadow + ((size_t)ch.scene * nl + light) * S * S;
-            for (int k = (int)threadIdx.x; k < kWin * kWin; k += 256) {
-                const unsigned v = win[(k / kWin) * kPitch + (k % kWin)];
-                const int x = wx0 + (k % kWin), y = wy0 + (k / kWin);
+            const unsigned n = wny << wsh, cmask = (1u << wsh) - 1u;
+            for (unsigned k = threadIdx.x; k < n; k += 256) {
+                const unsigned v = win[(k >> wsh) * kPitch + (k & cmask)];
+                const int x = wx0 + (int)(k & cmask), y = wy0 + (int)(k >> wsh);
                 if (v != 0x3F800000u && x < S && y < S) atomicMin(sm + (size_t)y * S + x, v);
             }
+            __syncthreads();      // the window is free for the next light
         }
-        __syncthreads();
 #endif
     }
     __syncthreads();
@@ -1186,7 +1276,7 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_shadow_large(slhip_m
                                                       const slhip_draw* __restrict__ draws, int S,
                                                       unsigned* __restrict__ shadow,
                                                       const unsigned* __restrict__ queue, unsigned capacity,
-                                                      const float4* __restrict__ clipbuf, unsigned n_clip_verts, int nl)
+                                                      const float4* __restrict__ clipbuf, unsigned n_clip_verts, int nl, int wide)
 {
     const unsigned count = min(queue[0], capacity);
     const QItem* items = reinterpret_cast<const QItem*>(queue + 4);
@@ -1219,9 +1309,9 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_shadow_large(slhip_m
         const int py = (int)((it.tile >> 16) << 3) + (int)(lane >> 3);
         if (px < t.xmin || px > t.xmax || py < t.ymin || py > t.ymax) continue;
         float l[3];
-        if (!coverage(t, px, py, l)) continue;
+        if (!coverage_walk(t, px, py, l, wide)) continue;
         ShadowTarget tgt;
-        tgt.win = nullptr; tgt.wx0 = 0; tgt.wy0 = 0;
+        tgt.win = nullptr; tgt.wx0 = 0; tgt.wy0 = 0; tgt.wnx = 0u; tgt.wny = 0u;
         tgt.sm = shadow + ((size_t)scene * nl + light) * S * S;
         tgt.W = S;
         tgt.emit(t, px, py, l);
@@ -2598,8 +2688,11 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
     // 4 S^2 bytes per scene and unused light (lights beyond the count cast no shadow)
     // bounding boxes up to this many pixels are walked by the triangle's own thread, larger ones go to the tile queue
     // (developer knobs; on the C2 scenes 48 / 16 instead of 128 cost the shadow pass +16 % / +100 %)
-    static const int raster_small = getenv("SLHIP_RASTER_SMALL") ? atoi(getenv("SLHIP_RASTER_SMALL")) : kSmallArea;
-    static const int shadow_small = getenv("SLHIP_SHADOW_SMALL") ? atoi(getenv("SLHIP_SHADOW_SMALL")) : kSmallArea;
+    // (read at every call, like SLHIP_SSAO_DEBUG: a test sends every triangle to the tile-queue kernels in-process with 0)
+    const int raster_small = getenv("SLHIP_RASTER_SMALL") ? atoi(getenv("SLHIP_RASTER_SMALL")) : kSmallArea;
+    const int shadow_small = getenv("SLHIP_SHADOW_SMALL") ? atoi(getenv("SLHIP_SHADOW_SMALL")) : kSmallArea;
+    // developer knob: 1 = the 64-bit edge arithmetic everywhere, the in-library reference of the 32-bit walk (slhip_raster_walk.h)
+    const int raster_wide = getenv("SLHIP_RASTER_WIDE") ? atoi(getenv("SLHIP_RASTER_WIDE")) : 0;
     const int NL = scratch->shadow_lights == 0u ? SLHIP_NUM_LIGHTS : (int)min(scratch->shadow_lights, (uint32_t)SLHIP_NUM_LIGHTS);
     if (n_chunks > 0 && (!scratch->d_clip || scratch->n_clip_verts == 0)) {
         slhip::set_error("slhip_render: d_clip scratch (n_clip_verts x 16 B x planes) is required");
@@ -2665,11 +2758,11 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
         SLHIP_CHECK(hipMemsetAsync(scratch->d_queue, 0, 16, stream));
         k_shadow_raster<<<n_chunks, 256, 0, stream>>>(
             *pool, d_scenes, d_draws, d_chunks, S, reinterpret_cast<unsigned*>(scratch->d_shadow),
-            scratch->d_queue, scratch->queue_capacity, clipbuf, scratch->n_clip_verts, scratch->d_shadow_tiles, NL, shadow_small);
+            scratch->d_queue, scratch->queue_capacity, clipbuf, scratch->n_clip_verts, scratch->d_shadow_tiles, NL, shadow_small, raster_wide);
         mark(1, stream);
         k_shadow_large<<<2048, 256, 0, stream>>>(*pool, d_scenes, d_draws, S,
                                                  reinterpret_cast<unsigned*>(scratch->d_shadow), scratch->d_queue,
-                                                 scratch->queue_capacity, clipbuf, scratch->n_clip_verts, NL);
+                                                 scratch->queue_capacity, clipbuf, scratch->n_clip_verts, NL, raster_wide);
         SLHIP_LAUNCH_CHECK();
     }
 
@@ -2682,10 +2775,10 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
         if (!d_depth_peel)
             k_raster<false><<<n_chunks, 256, 0, stream>>>(*pool, d_scenes, d_draws, d_chunks, n_chunks, W, H, d_depth_peel,
                                                           reinterpret_cast<unsigned long long*>(scratch->d_vis),
-                                                          scratch->d_queue, scratch->queue_capacity, clipbuf, screen, raster_small);
+                                                          scratch->d_queue, scratch->queue_capacity, clipbuf, screen, raster_small, raster_wide);
         k_raster<true><<<d_depth_peel ? n_chunks : min(n_chunks, 4096u), 256, 0, stream>>>(
             *pool, d_scenes, d_draws, d_chunks, n_chunks, W, H, d_depth_peel, reinterpret_cast<unsigned long long*>(scratch->d_vis),
-            scratch->d_queue, scratch->queue_capacity, clipbuf, screen, raster_small);
+            scratch->d_queue, scratch->queue_capacity, clipbuf, screen, raster_small, raster_wide);
         mark(3, stream);
         k_large<<<2048, 256, 0, stream>>>(*pool, d_scenes, d_draws, W, H,
                                           reinterpret_cast<unsigned long long*>(scratch->d_vis), scratch->d_queue,

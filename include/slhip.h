@@ -233,13 +233,15 @@ typedef struct {
     float*    d_ao;           /* f32 [B,H,W] occlusion + f32 [B,H+2,W+2] camera-z plane + per 8 x 8 tile a
                                  float2 record and a skip byte (SSAO; slhip_render_scratch_bytes sizes it) */
     float*    d_shadow;       /* f32 [B,NUM_LIGHTS,S,S] shadow depth (only active lights)    */
-    uint32_t* d_queue;        /* large-triangle work queue: [0]=count, then (prim,tile) pairs */
+    uint32_t* d_queue;        /* large-triangle work queue, 16-byte aligned: a 16-byte header ([0] entries, [1] the
+                                 8 x 8 tiles of their pixel boxes), then one 32-byte entry per queued triangle   */
     float*    d_lum;          /* f32 [B,4] HDR sums for auto exposure                        */
     float*    d_clip;         /* f32 [1 + NUM_LIGHTS][n_clip_verts][4]: clip positions written by the
                                  MFMA vertex-transform kernel (plane 0: camera, 1..3: lights)  */
     uint32_t* d_shadow_tiles; /* u32 [B][NUM_LIGHTS][ceil(ceil(S/64)^2 / 32)]: touched-tile bits (see
                                  SLHIP_RENDER_SHADOW_RESET)                                     */
-    uint32_t  queue_capacity; /* number of (prim,tile) pairs that fit                        */
+    uint32_t  queue_capacity; /* 16-byte units of d_queue behind its header (an entry takes two); triangles
+                                 beyond it are rasterised by one thread each: the same picture, slowly          */
     uint32_t  shadow_res;     /* S (reference: 2048, render_pass.cpp:271)                    */
     uint32_t  n_clip_verts;   /* sum of n_verts over the draws of the batch                  */
     uint32_t  shadow_lights;  /* light maps per scene in d_shadow: 0 = SLHIP_NUM_LIGHTS; 1 or 2 = d_shadow is

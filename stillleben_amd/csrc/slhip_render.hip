@@ -6,9 +6,10 @@
 //              transform chain, near clipping, 1/256-px snapping, exact integer edge functions.
 //              Small triangles are resolved by the owning thread with a 64-bit atomicMin on the
 //              visibility buffer (key = depth24 << 32 | primitive id, so the depth test AND the
-//              GL draw-order tie-break are one atomic); larger ones are split into 8x8-pixel
-//              tile items, compacted into a work queue with one wave-aggregated atomic per wave.
-//   k_large    one wave per (triangle, 8x8 tile) item: lane == pixel.
+//              GL draw-order tie-break are one atomic); larger ones go to a work queue, one
+//              entry per triangle (slhip_tile_queue.h).
+//   k_large    one wave per 8x8-pixel tile of a queued triangle's box: lane == pixel.  The waves
+//              share the queue's tiles evenly and enumerate them from the entries.
 //   k_shade    deferred: one thread per pixel decodes the winning primitive, re-runs the
 //              vertex stage for its three vertices, reproduces the interpolation of the
 //              fixed-function pipeline and evaluates the fragment shader; writes the selected
@@ -27,6 +28,7 @@
 #include "slhip_common.h"
 #include "slhip_cubemap.h"
 #include "slhip_raster_walk.h"
+#include "slhip_tile_queue.h"
 
 // Occupancy ceilings of the render kernels (waves per SIMD; 0 = whatever the registers allow; build-time experiment knobs).  In
 // the pipeline the settle stream is the critical path -- 2400 dependent launches whose single-wave blocks have to find a free
@@ -74,7 +76,7 @@ static_assert(sizeof(slhip_chunk) == 16, "slhip_chunk layout");
 constexpr float kInvalid = 3000.0f;  // render_pass.cpp:316
 constexpr float kPi = 3.141592653589793f;
 constexpr unsigned long long kVisEmpty = ~0ull;
-constexpr int kSmallArea = 256;  // bbox pixels a single thread rasterises itself (larger boxes: tile queue); 128 / 256 / 1024 measured: shadow pass 17.2 / 16.7 / 16.4 ms
+constexpr int kSmallArea = 256;  // bbox pixels a single thread rasterises itself (larger boxes: tile queue); 128 / 256 / 1024 measured: shadow pass 17.2 / 16.7 / 16.4 ms; with one queue entry per triangle 128 / 256 / 512 / 1024: shadow raster + large 10.86 / 10.41 / 10.24 / 10.31, visibility 5.93 / 5.88 / 5.87 / 5.83 (profiles/r09)
 
 // ---------------------------------------------------------------------------------------------
 // fixed-order arithmetic (R1)
@@ -775,12 +777,37 @@ struct ShadowTarget {
     }
 };
 
-// work item of the large-triangle queue
-struct QItem {
-    unsigned draw;      // global draw index
-    unsigned tri_sub;   // triangle | sub-triangle << 31
-    unsigned scene_aux; // scene | light << 24
-    unsigned tile;      // tx | ty << 16   (8x8 pixel tiles)
+// A consumer wave's share of the large-triangle queue (slhip_tile_queue.h).  All of it is the same in every lane of the wave
+// (the wave index goes through readfirstlane so that the compiler knows): header, entries and the binary search are scalar loads.
+struct QueueShare {
+    const slhip_tq::Entry* entries;
+    slhip_tq::Walk walk;
+    __device__ __forceinline__ QueueShare(const unsigned* __restrict__ queue, unsigned capacity)
+    {
+        const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+        const unsigned n_waves = (gridDim.x * blockDim.x) >> 6;
+        entries = reinterpret_cast<const slhip_tq::Entry*>(queue + slhip_tq::kHeaderWords);
+        walk.first(slhip_tq::plan_of(queue[0], queue[1], queue[2], capacity), entries, n_waves, wave);
+    }
+};
+
+// The lane's pixel in the tiles [k0, k1) of an entry's box, one after the other (k = ty * ntx + tx): one division per entry
+// and wave, then a counter.
+struct TilePixels {
+    unsigned ntx, tx, ty;
+    int px0, py0;        // the lane's pixel in the box's first tile
+    __device__ __forceinline__ TilePixels(const slhip_tq::Entry& en, unsigned k0, unsigned lane)
+    {
+        ntx = slhip_tq::ntx(en);
+        ty = k0 / ntx; tx = k0 - ty * ntx;
+        px0 = (int)((en.t0 & 0xFFFFu) << 3) + (int)(lane & 7);
+        py0 = (int)((en.t0 >> 16) << 3) + (int)(lane >> 3);
+    }
+    __device__ __forceinline__ void next(int& px, int& py)
+    {
+        px = px0 + (int)(tx << 3); py = py0 + (int)(ty << 3);
+        if (++tx == ntx) { tx = 0u; ++ty; }
+    }
 };
 
 // All pixels of the triangle's bounding box by one thread.  The edge functions are exact integers,
@@ -849,30 +876,20 @@ __device__ __forceinline__ void raster_or_enqueue(const Setup& t, const Target& 
     const int bw = t.xmax - t.xmin + 1, bh = t.ymax - t.ymin + 1;
     bool in_place = bw * bh <= small_area;
     if (!in_place) {
-        const int tx0 = t.xmin >> 3, tx1 = t.xmax >> 3, ty0 = t.ymin >> 3, ty1 = t.ymax >> 3;
-        const unsigned n = (unsigned)((tx1 - tx0 + 1) * (ty1 - ty0 + 1));
-        const unsigned base = atomicAdd(queue, n);
-        if (base + n <= capacity) {
-            QItem* items = reinterpret_cast<QItem*>(queue + 4);
-            unsigned k = base;
-            for (int ty = ty0; ty <= ty1; ++ty)
-                for (int tx = tx0; tx <= tx1; ++tx) {
-                    QItem it;
-                    it.draw = draw; it.tri_sub = tri_sub; it.scene_aux = scene_aux;
-                    it.tile = (unsigned)tx | ((unsigned)ty << 16);
-                    items[k++] = it;
-                }
-        } else {
-            // queue full: fall back to the (slow) in-place loop; mark the reservation as void
-            // by writing empty items where it overlaps the queue
-            QItem* items = reinterpret_cast<QItem*>(queue + 4);
-            for (unsigned k = base; k < min(base + n, capacity); ++k) {
-                QItem it;
-                it.draw = 0xFFFFFFFFu; it.tri_sub = 0; it.scene_aux = 0; it.tile = 0;
-                items[k] = it;
-            }
-            in_place = true;
+        // one entry for the triangle: the consumers enumerate the 8 x 8 tiles of its box (slhip_tile_queue.h)
+        const unsigned tx0 = (unsigned)(t.xmin >> 3), ty0 = (unsigned)(t.ymin >> 3);
+        const unsigned ntx = (unsigned)(t.xmax >> 3) - tx0 + 1u, nty = (unsigned)(t.ymax >> 3) - ty0 + 1u;
+        const unsigned n = ntx * nty;
+        const slhip_tq::Slot s =
+            slhip_tq::slot_of(atomicAdd(reinterpret_cast<unsigned long long*>(queue), slhip_tq::reservation(n)), n, capacity);
+        if (s.carried) atomicOr(queue + 2, 1u);
+        if (s.fits) {
+            uint4* e = reinterpret_cast<uint4*>(queue + slhip_tq::kHeaderWords) + slhip_tq::kUnitsPerEntry * (size_t)s.index;
+            e[0] = make_uint4(draw, tri_sub, scene_aux, s.tile_base);
+            e[1] = make_uint4(tx0 | (ty0 << 16), s.carried ? 0u : (ntx | (nty << 16)), 0u, 0u);
         }
+        // queue full (or the tile counter at its end): the (slow) in-place loop; the tiles stay reserved with no entry behind them
+        in_place = !s.fits || s.carried;
     }
     if (in_place) raster_bbox(t, tgt, wide);
 }
@@ -1013,71 +1030,62 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_raster(slhip_mesh_po
 }
 
 // k_large: one wave per (triangle, 8x8 tile); lane == pixel.  Every wave takes a CONTIGUOUS run of
-// queue items: the tiles of one triangle sit next to each other in the queue, so the fetch, the
-// near-plane clip and the setup are done once per run of equal triangles, not once per tile.
+// the queue's tiles and enumerates them from the entries (slhip_tile_queue.h): the fetch, the
+// near-plane clip and the setup are done once per entry and wave, and nothing is loaded per tile.
 __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_large(slhip_mesh_pool pool, const slhip_scene* __restrict__ scenes,
                                                const slhip_draw* __restrict__ draws, int W, int H,
                                                unsigned long long* __restrict__ vis,
                                                const unsigned* __restrict__ queue, unsigned capacity,
                                                const float4* __restrict__ clipbuf, const uint4* __restrict__ screen)
 {
-    const unsigned count = min(queue[0], capacity);
-    const QItem* items = reinterpret_cast<const QItem*>(queue + 4);
+    const QueueShare q(queue, capacity);
     const unsigned lane = threadIdx.x & 63;
-    const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const unsigned n_waves = (gridDim.x * blockDim.x) >> 6;
-    const unsigned per = (count + n_waves - 1) / n_waves;
-    const unsigned i0 = wave * per, i1 = min(i0 + per, count);
-    unsigned p_draw = 0xFFFFFFFFu, p_tri = 0u, p_scene = 0u, prim = 0u;
-    bool ok = false;
-    Setup t;
-    for (unsigned i = i0; i < i1; ++i) {
-        const QItem it = items[i];
-        if (it.draw == 0xFFFFFFFFu) continue;
-        if (it.draw != p_draw || it.tri_sub != p_tri || it.scene_aux != p_scene) {
-            p_draw = it.draw; p_tri = it.tri_sub; p_scene = it.scene_aux;
-            ok = false;
-            const slhip_draw* dr = draws + it.draw;
-            const unsigned tri = it.tri_sub & 0x7FFFFFFFu;
-            const int sub = (int)(it.tri_sub >> 31);
-            const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
-            ClipVert cv[3];
-            const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
-            const bool cached = screen_all_inside(s0, s1, s2);
-            if (cached && (sub != 0 || !setup_from_screen(s0, s1, s2, W, H, t))) continue;
-            if (!cached) {
+    for (unsigned e = q.walk.e0; e < q.walk.e1; ++e) {
+        const slhip_tq::Entry en = q.entries[e];
+        if (q.walk.done(en)) break;
+        unsigned k0, k1;
+        if (!q.walk.tiles(en, k0, k1)) continue;
+        Setup t;
+        const slhip_draw* dr = draws + en.draw;
+        const unsigned tri = en.tri_sub & 0x7FFFFFFFu;
+        const int sub = (int)(en.tri_sub >> 31);
+        const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
+        ClipVert cv[3];
+        const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
+        const bool cached = screen_all_inside(s0, s1, s2);
+        if (cached && (sub != 0 || !setup_from_screen(s0, s1, s2, W, H, t))) continue;
+        if (!cached) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float4 c4 = clipbuf[dr->clip_base + ip[k]];
-                    cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-                    cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
-                }
-                ClipVert poly[4];
-                const int n = clip_near(cv, poly);
-                if (sub > n - 3) continue;
-                const ClipVert& pb = sub == 0 ? poly[1] : poly[2];
-                const ClipVert& pc = sub == 0 ? poly[2] : poly[3];
-                if (!setup_tri(poly[0].clip, pb.clip, pc.clip, W, H, t)) continue;
+            for (int k = 0; k < 3; ++k) {
+                const float4 c4 = clipbuf[dr->clip_base + ip[k]];
+                cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
+                cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
             }
-            prim = dr->prim_base + tri;
-            ok = true;
+            ClipVert poly[4];
+            const int n = clip_near(cv, poly);
+            if (sub > n - 3) continue;
+            const ClipVert& pb = sub == 0 ? poly[1] : poly[2];
+            const ClipVert& pc = sub == 0 ? poly[2] : poly[3];
+            if (!setup_tri(poly[0].clip, pb.clip, pc.clip, W, H, t)) continue;
         }
-        if (!ok) continue;
-        const int px = (int)((it.tile & 0xFFFFu) << 3) + (int)(lane & 7);
-        const int py = (int)((it.tile >> 16) << 3) + (int)(lane >> 3);
-        if (px < t.xmin || px > t.xmax || py < t.ymin || py > t.ymax) continue;
-        float l[3];
-        // (the 64-bit coverage: what is queued here is the plane's two triangles and little else, and they never fit the narrow
-        // form -- with the choice in the loop the phase went from 2.55 to 2.66 ms per 1024 C2 scenes, profiles/r08)
-        if (!coverage(t, px, py, l)) continue;
         MainTarget tgt;
-        tgt.vis = vis + (size_t)it.scene_aux * W * H;
+        tgt.vis = vis + (size_t)en.scene_aux * W * H;
         tgt.peel = nullptr;
         tgt.W = W;
-        tgt.prim = prim;
+        tgt.prim = dr->prim_base + tri;
         tgt.need_attr = false;
         tgt.pool_tex = nullptr;
-        tgt.emit(t, px, py, l);
+        TilePixels tp(en, k0, lane);
+        for (unsigned k = k0; k < k1; ++k) {
+            int px, py;
+            tp.next(px, py);
+            if (px < t.xmin || px > t.xmax || py < t.ymin || py > t.ymax) continue;
+            float l[3];
+            // (the 64-bit coverage: what is queued here is the plane's two triangles and little else, and they never fit the narrow
+            // form -- with the choice in the loop the phase went from 2.55 to 2.66 ms per 1024 C2 scenes, profiles/r08)
+            if (!coverage(t, px, py, l)) continue;
+            tgt.emit(t, px, py, l);
+        }
     }
 }
 
@@ -1278,43 +1286,35 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_shadow_large(slhip_m
                                                       const unsigned* __restrict__ queue, unsigned capacity,
                                                       const float4* __restrict__ clipbuf, unsigned n_clip_verts, int nl, int wide)
 {
-    const unsigned count = min(queue[0], capacity);
-    const QItem* items = reinterpret_cast<const QItem*>(queue + 4);
+    // contiguous runs of tiles per wave, setup once per entry and wave (see k_large)
+    const QueueShare q(queue, capacity);
     const unsigned lane = threadIdx.x & 63;
-    const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const unsigned n_waves = (gridDim.x * blockDim.x) >> 6;
-    // contiguous runs per wave, setup shared by the tiles of one triangle (see k_large)
-    const unsigned per = (count + n_waves - 1) / n_waves;
-    const unsigned i0 = wave * per, i1 = min(i0 + per, count);
-    unsigned p_draw = 0xFFFFFFFFu, p_tri = 0u, p_scene = 0u;
-    bool ok = false;
-    Setup t;
-    for (unsigned i = i0; i < i1; ++i) {
-        const QItem it = items[i];
-        if (it.draw == 0xFFFFFFFFu) continue;
-        const unsigned scene = it.scene_aux & 0xFFFFFFu;
-        const int light = (int)(it.scene_aux >> 24);
-        if (it.draw != p_draw || it.tri_sub != p_tri || it.scene_aux != p_scene) {
-            p_draw = it.draw; p_tri = it.tri_sub; p_scene = it.scene_aux;
-            ok = false;
-            const slhip_draw* dr = draws + it.draw;
-            const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)it.tri_sub;
-            const float4* plane = clipbuf + (size_t)(1 + light) * n_clip_verts + dr->clip_base;
-            const uint4* sp = reinterpret_cast<const uint4*>(plane);
-            if (!setup_from_screen(sp[ip[0]], sp[ip[1]], sp[ip[2]], S, S, t)) continue;
-            ok = true;
-        }
-        if (!ok) continue;
-        const int px = (int)((it.tile & 0xFFFFu) << 3) + (int)(lane & 7);
-        const int py = (int)((it.tile >> 16) << 3) + (int)(lane >> 3);
-        if (px < t.xmin || px > t.xmax || py < t.ymin || py > t.ymax) continue;
-        float l[3];
-        if (!coverage_walk(t, px, py, l, wide)) continue;
+    for (unsigned e = q.walk.e0; e < q.walk.e1; ++e) {
+        const slhip_tq::Entry en = q.entries[e];
+        if (q.walk.done(en)) break;
+        unsigned k0, k1;
+        if (!q.walk.tiles(en, k0, k1)) continue;
+        const unsigned scene = en.scene_aux & 0xFFFFFFu;
+        const int light = (int)(en.scene_aux >> 24);
+        Setup t;
+        const slhip_draw* dr = draws + en.draw;
+        const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)en.tri_sub;
+        const float4* plane = clipbuf + (size_t)(1 + light) * n_clip_verts + dr->clip_base;
+        const uint4* sp = reinterpret_cast<const uint4*>(plane);
+        if (!setup_from_screen(sp[ip[0]], sp[ip[1]], sp[ip[2]], S, S, t)) continue;
         ShadowTarget tgt;
         tgt.win = nullptr; tgt.wx0 = 0; tgt.wy0 = 0; tgt.wnx = 0u; tgt.wny = 0u;
         tgt.sm = shadow + ((size_t)scene * nl + light) * S * S;
         tgt.W = S;
-        tgt.emit(t, px, py, l);
+        TilePixels tp(en, k0, lane);
+        for (unsigned k = k0; k < k1; ++k) {
+            int px, py;
+            tp.next(px, py);
+            if (px < t.xmin || px > t.xmax || py < t.ymin || py > t.ymax) continue;
+            float l[3];
+            if (!coverage_walk(t, px, py, l, wide)) continue;
+            tgt.emit(t, px, py, l);
+        }
     }
 }
 

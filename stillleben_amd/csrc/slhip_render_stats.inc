@@ -298,68 +298,60 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_os_raster(slhip_mesh
     }
 }
 
-// k_large with the silhouette target: one wave per contiguous run of queue items, lane == pixel of the 8 x 8 tile; the wave's
-// ballot is the tile's word, one atomicOr per (triangle, tile).  Set-up and item handling are wave-uniform, so every lane
-// reaches the ballot.
+// k_large with the silhouette target: one wave per contiguous run of the queue's tiles, lane == pixel of the 8 x 8 tile; the
+// wave's ballot is the tile's word, one atomicOr per (triangle, tile).  Set-up and tile enumeration are wave-uniform, so every
+// lane reaches the ballot.
 __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_os_large(slhip_mesh_pool pool, const slhip_draw* __restrict__ draws, int W, int H,
                                                   const OsRec* __restrict__ out, unsigned n_slots,
                                                   unsigned long long* __restrict__ pool_words,
                                                   const unsigned* __restrict__ queue, unsigned capacity,
                                                   const float4* __restrict__ clipbuf, const uint4* __restrict__ screen)
 {
-    const unsigned count = min(queue[0], capacity);
-    const QItem* items = reinterpret_cast<const QItem*>(queue + 4);
+    const QueueShare q(queue, capacity);
     const unsigned lane = threadIdx.x & 63;
-    const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const unsigned n_waves = (gridDim.x * blockDim.x) >> 6;
-    const unsigned per = (count + n_waves - 1) / n_waves;
-    const unsigned i0 = wave * per, i1 = min(i0 + per, count);
-    unsigned p_draw = 0xFFFFFFFFu, p_tri = 0u, p_scene = 0u;
-    bool ok = false;
-    Setup t;
-    StatsTarget tgt;
-    for (unsigned i = i0; i < i1; ++i) {
-        const QItem it = items[i];
-        if (it.draw == 0xFFFFFFFFu) continue;
-        if (it.draw != p_draw || it.tri_sub != p_tri || it.scene_aux != p_scene) {
-            p_draw = it.draw; p_tri = it.tri_sub; p_scene = it.scene_aux;
-            ok = false;
-            const slhip_draw* dr = draws + it.draw;
-            if (!os_target(out, n_slots, it.scene_aux, dr, pool_words, tgt)) continue;
-            const unsigned tri = it.tri_sub & 0x7FFFFFFFu;
-            const int sub = (int)(it.tri_sub >> 31);
-            const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
-            const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
-            const bool cached = screen_all_inside(s0, s1, s2);
-            if (cached && (sub != 0 || !setup_from_screen(s0, s1, s2, W, H, t))) continue;
-            if (!cached) {
-                ClipVert cv[3];
+    for (unsigned e = q.walk.e0; e < q.walk.e1; ++e) {
+        const slhip_tq::Entry en = q.entries[e];
+        if (q.walk.done(en)) break;
+        unsigned k0, k1;
+        if (!q.walk.tiles(en, k0, k1)) continue;
+        Setup t;
+        StatsTarget tgt;
+        const slhip_draw* dr = draws + en.draw;
+        if (!os_target(out, n_slots, en.scene_aux, dr, pool_words, tgt)) continue;
+        const unsigned tri = en.tri_sub & 0x7FFFFFFFu;
+        const int sub = (int)(en.tri_sub >> 31);
+        const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
+        const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
+        const bool cached = screen_all_inside(s0, s1, s2);
+        if (cached && (sub != 0 || !setup_from_screen(s0, s1, s2, W, H, t))) continue;
+        if (!cached) {
+            ClipVert cv[3];
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float4 c4 = clipbuf[dr->clip_base + ip[k]];
-                    cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-                    cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
-                }
-                ClipVert poly[4];
-                const int n = clip_near(cv, poly);
-                if (sub > n - 3) continue;
-                const ClipVert& pb = sub == 0 ? poly[1] : poly[2];
-                const ClipVert& pc = sub == 0 ? poly[2] : poly[3];
-                if (!setup_tri(poly[0].clip, pb.clip, pc.clip, W, H, t)) continue;
+            for (int k = 0; k < 3; ++k) {
+                const float4 c4 = clipbuf[dr->clip_base + ip[k]];
+                cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
+                cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
             }
-            ok = true;
+            ClipVert poly[4];
+            const int n = clip_near(cv, poly);
+            if (sub > n - 3) continue;
+            const ClipVert& pb = sub == 0 ? poly[1] : poly[2];
+            const ClipVert& pc = sub == 0 ? poly[2] : poly[3];
+            if (!setup_tri(poly[0].clip, pb.clip, pc.clip, W, H, t)) continue;
         }
-        if (!ok) continue;
-        const int px = (int)((it.tile & 0xFFFFu) << 3) + (int)(lane & 7);
-        const int py = (int)((it.tile >> 16) << 3) + (int)(lane >> 3);
-        bool cov = !(px < t.xmin || px > t.xmax || py < t.ymin || py > t.ymax);
-        float l[3];
-        cov = cov && coverage(t, px, py, l);
-        cov = cov && tgt.passes(t, px, py, l);
-        const unsigned long long bits = __ballot(cov);   // bit lane == bit (py & 7) * 8 + (px & 7)
-        if (lane == 0 && bits != 0ull) {
-            unsigned long long* w = tgt.word(px, py);
-            if (w) atomicOr(w, bits);
+        TilePixels tp(en, k0, lane);
+        for (unsigned k = k0; k < k1; ++k) {
+            int px, py;
+            tp.next(px, py);
+            bool cov = !(px < t.xmin || px > t.xmax || py < t.ymin || py > t.ymax);
+            float l[3];
+            cov = cov && coverage(t, px, py, l);
+            cov = cov && tgt.passes(t, px, py, l);
+            const unsigned long long bits = __ballot(cov);   // bit lane == bit (py & 7) * 8 + (px & 7)
+            if (lane == 0 && bits != 0ull) {
+                unsigned long long* w = tgt.word(px, py);
+                if (w) atomicOr(w, bits);
+            }
         }
     }
 }

@@ -11,15 +11,6 @@ namespace slhip {
 
 void set_error(const char* fmt, ...);
 
-// slhip_object_keypoints.hip: farthest point sampling per class for any count in [1, limit] -- the body of
-// slhip_object_keypoints_fps / _fps_host, which slhip_object_regions_centres / _centres_host run with their own limit.
-int fps_device(const char* who, const char* what, uint32_t limit, const float* d_pos, uint64_t n_vertices, const slhip_asset* d_assets,
-               uint32_t n_assets, const slhip_draw* d_templates, uint32_t n_templates, uint32_t n_fps, uint64_t max_verts,
-               void* d_scratch, float* d_keypoints, int32_t* d_vertex, hipStream_t stream);
-int fps_host(const char* who, const char* what, uint32_t limit, const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets,
-             uint32_t n_assets, const slhip_draw* h_templates, uint32_t n_templates, uint32_t n_fps, float* h_keypoints,
-             int32_t* h_vertex);
-
 #define SLHIP_CHECK(expr)                                                                     \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \

@@ -3,9 +3,7 @@
 // include/slhip.h "Object crops" and DESIGN.md "Object crops" are the contract; tests/object_crops_ref.py restates it in the
 // same float32 operation order (IEEE add, mul, div, floor, compare under -ffp-contract=off), so records and windows are
 // bit-exact against it.
-//   k_crop_count   one wave per scene: the eligible slots, ballot + popcount over the slots in strides of 64
-//   k_scan_counts  (slhip_scan.h) one block: exclusive scan of the per-scene counts, the total behind them
-//   k_crop_emit    the walk of k_crop_count again; every eligible lane writes its record at the scene's offset + its rank
+//   select         the count / scan / emit pass of slhip_select.h under CropRule
 //   k_crop_gather  one thread per output pixel, 256 consecutive pixels of one crop per block: a pure streaming kernel
 #include <hip/hip_runtime.h>
 
@@ -14,9 +12,11 @@
 #include <cstdint>
 
 #include "slhip.h"
+#include "slhip_checks.h"
 #include "slhip_common.h"
 #include "slhip_rng.h"
-#include "slhip_scan.h"
+#include "slhip_select.h"
+#include "slhip_step_timer.h"
 
 namespace {
 
@@ -29,72 +29,51 @@ constexpr uint32_t STREAM_CROP = 5u;      // "Randomness" of include/slhip.h
 
 using Params = slhip_object_crop_params;
 
-__device__ __forceinline__ bool eligible(const Params& p, const slhip_object_stats& s)
-{
-    const int32_t* b = p.box ? s.bbox_obj : s.bbox_visib;
-    return b[2] > 0 && b[3] > 0 && s.px_visib >= p.min_px && (float)s.px_visib >= p.min_visib_fract * (float)s.px_all;
-}
-
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
-__device__ slhip_object_crop make_record(const Params& p, const slhip_object_stats& s, uint32_t scene, uint32_t slot)
-{
-    const int32_t* b = p.box ? s.bbox_obj : s.bbox_visib;
-    const float w = (float)b[2], h = (float)b[3];
-    slhip::Philox ph;
-    ph.c[0] = p.scene_id_base + scene; ph.c[1] = STREAM_CROP; ph.c[2] = slot; ph.c[3] = 0x51DE5EEDu;
-    ph.k[0] = p.seed_lo; ph.k[1] = p.seed_hi;
-    ph.block();
-    const float u0 = u01(ph.c[0]), u1 = u01(ph.c[1]), u2 = u01(ph.c[2]);
-    const float side0 = (float)max(b[2], b[3]) * p.pad;
-    const float side = side0 * (1.0f + p.jitter_scale * (2.0f * u0 - 1.0f));
-    const float cxb = ((float)b[0] + 0.5f * w) + p.jitter_shift * w * (2.0f * u1 - 1.0f);
-    const float cyb = ((float)b[1] + 0.5f * h) + p.jitter_shift * h * (2.0f * u2 - 1.0f);
-    slhip_object_crop r;
-    r.scene = scene; r.slot = slot;
-    r.x0 = cxb - 0.5f * side;
-    r.y0 = cyb - 0.5f * side;
-    r.side = side;
-    r.step = side / (float)p.size;
-    r.K[0] = p.fx / r.step; r.K[1] = p.fy / r.step;
-    r.K[2] = (p.cx - r.x0) / r.step; r.K[3] = (p.cy - r.y0) / r.step;
-    r._pad[0] = r._pad[1] = 0u;
-    return r;
-}
+// the rule of slhip_select.h: a slot with a box, enough visible pixels and a large enough visible share gets a window
+struct CropRule {
+    typedef slhip_object_crop Record;
+    typedef slhip_object_crop_params Params;
+    Params p;
+    const slhip_object_stats* stats;
 
-// blocks of four waves, one scene per wave; the loop bounds are the same in every lane of a wave, so every ballot sees all 64
-__global__ __launch_bounds__(256) void k_crop_count(Params p, const slhip_object_stats* __restrict__ stats, uint32_t n_scenes,
-                                                    uint32_t n_slots, unsigned long long* __restrict__ counts)
-{
-    const uint32_t scene = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (scene >= n_scenes) return;
-    const slhip_object_stats* row = stats + (size_t)scene * n_slots;
-    unsigned long long n = 0ull;
-    for (uint32_t base = 1u; base < n_slots; base += 64u) {
-        const uint32_t slot = base + lane;
-        const bool ok = slot < n_slots && eligible(p, row[slot]);
-        n += (unsigned long long)__popcll(__ballot(ok));
+    __device__ __forceinline__ const slhip_object_stats* row(uint32_t scene, uint32_t n_slots) const
+    {
+        return stats + (size_t)scene * n_slots;
     }
-    if (lane == 0u) counts[scene] = n;
-}
-
-__global__ __launch_bounds__(256) void k_crop_emit(Params p, const slhip_object_stats* __restrict__ stats, uint32_t n_scenes,
-                                                   uint32_t n_slots, const unsigned long long* __restrict__ offsets,
-                                                   slhip_object_crop* __restrict__ crops, unsigned long long capacity)
-{
-    const uint32_t scene = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (scene >= n_scenes) return;
-    const slhip_object_stats* row = stats + (size_t)scene * n_slots;
-    unsigned long long at = offsets[scene];
-    for (uint32_t base = 1u; base < n_slots; base += 64u) {
-        const uint32_t slot = base + lane;
-        const bool ok = slot < n_slots && eligible(p, row[slot]);
-        const unsigned long long votes = __ballot(ok);
-        const unsigned long long mine = at + (unsigned long long)__popcll(votes & ((1ull << lane) - 1ull));
-        if (ok && mine < capacity) crops[mine] = make_record(p, row[slot], scene, slot);
-        at += (unsigned long long)__popcll(votes);
+    __device__ __forceinline__ bool eligible(const slhip_object_stats* row, uint32_t slot) const
+    {
+        const slhip_object_stats& s = row[slot];
+        const int32_t* b = p.box ? s.bbox_obj : s.bbox_visib;
+        return b[2] > 0 && b[3] > 0 && s.px_visib >= p.min_px && (float)s.px_visib >= p.min_visib_fract * (float)s.px_all;
     }
-}
+    __device__ Record make(const slhip_object_stats* row, uint32_t scene, uint32_t slot) const
+    {
+        const slhip_object_stats& s = row[slot];
+        const int32_t* b = p.box ? s.bbox_obj : s.bbox_visib;
+        const float w = (float)b[2], h = (float)b[3];
+        slhip::Philox ph;
+        ph.c[0] = p.scene_id_base + scene; ph.c[1] = STREAM_CROP; ph.c[2] = slot; ph.c[3] = 0x51DE5EEDu;
+        ph.k[0] = p.seed_lo; ph.k[1] = p.seed_hi;
+        ph.block();
+        const float u0 = u01(ph.c[0]), u1 = u01(ph.c[1]), u2 = u01(ph.c[2]);
+        const float side0 = (float)max(b[2], b[3]) * p.pad;
+        const float side = side0 * (1.0f + p.jitter_scale * (2.0f * u0 - 1.0f));
+        const float cxb = ((float)b[0] + 0.5f * w) + p.jitter_shift * w * (2.0f * u1 - 1.0f);
+        const float cyb = ((float)b[1] + 0.5f * h) + p.jitter_shift * h * (2.0f * u2 - 1.0f);
+        slhip_object_crop r;
+        r.scene = scene; r.slot = slot;
+        r.x0 = cxb - 0.5f * side;
+        r.y0 = cyb - 0.5f * side;
+        r.side = side;
+        r.step = side / (float)p.size;
+        r.K[0] = p.fx / r.step; r.K[1] = p.fy / r.step;
+        r.K[2] = (p.cx - r.x0) / r.step; r.K[3] = (p.cy - r.y0) / r.step;
+        r._pad[0] = r._pad[1] = 0u;
+        return r;
+    }
+};
 
 struct Source {
     const uint32_t* rgb;        // the four bytes of a pixel as one word
@@ -197,35 +176,20 @@ __global__ __launch_bounds__(256) void k_crop_gather(Params p, const slhip_objec
 }
 
 // optional HIP-event timing (tools/time_object_crops.py): events round the last select's kernels and the last gather's
-bool g_timing = false;
-hipEvent_t g_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-bool g_timed[2] = {false, false};
-
-bool is_finite(float v) { return v - v == 0.0f; }
+slhip::StepTimer<2> g_timer;
 
 }  // namespace
 
-extern "C" int slhip_object_crops_timing_enable(int on)
-{
-    if (on && !g_ev[0])
-        for (hipEvent_t& e : g_ev) SLHIP_CHECK(hipEventCreate(&e));
-    g_timing = on != 0;
-    g_timed[0] = g_timed[1] = false;
-    return 0;
-}
+extern "C" int slhip_object_crops_timing_enable(int on) { return g_timer.enable(on); }
 
 extern "C" int slhip_object_crops_timings(float ms_out[2])
 {
-    if (!ms_out || !g_timed[0] || !g_timed[1]) {
+    if (!ms_out || !g_timer.all_timed()) {
         slhip::set_error("slhip_object_crops_timings: no timed calls (slhip_object_crops_timing_enable(1), then "
                          "slhip_object_crops_select and slhip_object_crops_gather)");
         return -1;
     }
-    SLHIP_CHECK(hipEventSynchronize(g_ev[1]));
-    SLHIP_CHECK(hipEventSynchronize(g_ev[3]));
-    SLHIP_CHECK(hipEventElapsedTime(&ms_out[0], g_ev[0], g_ev[1]));
-    SLHIP_CHECK(hipEventElapsedTime(&ms_out[1], g_ev[2], g_ev[3]));
-    return 0;
+    return std::min(g_timer.read(ms_out), 0);
 }
 
 extern "C" int slhip_object_crops_check_params(const slhip_object_crop_params* p, int W, int H)
@@ -235,19 +199,16 @@ extern "C" int slhip_object_crops_check_params(const slhip_object_crop_params* p
         slhip::set_error("%s: null parameter record", who);
         return -1;
     }
-    if (W <= 0 || H <= 0 || (uint64_t)W * (uint64_t)H > 0x7fffffffu) {
+    if (!slhip::picture_fits(W, H, 0x7fffffff, 0x7fffffffu)) {
         slhip::set_error("%s: bad picture size %d x %d", who, W, H);
         return -1;
     }
-    if (p->size < 1u || p->size > (uint32_t)SLHIP_OBJECT_CROPS_MAX_SIZE) {
-        slhip::set_error("%s: size %u must be in [1, %d]", who, p->size, SLHIP_OBJECT_CROPS_MAX_SIZE);
-        return -1;
-    }
+    if (const int st = slhip::check_range(who, "size", p->size, 1u, SLHIP_OBJECT_CROPS_MAX_SIZE)) return st;
     if (p->box > 1u) {
         slhip::set_error("%s: box %u (0: bbox_visib, 1: bbox_obj)", who, p->box);
         return -1;
     }
-    if (!(p->pad > 0.0f) || !is_finite(p->pad)) {
+    if (!(p->pad > 0.0f) || !slhip::is_finite(p->pad)) {
         slhip::set_error("%s: pad %g must be positive and finite", who, (double)p->pad);
         return -1;
     }
@@ -267,11 +228,7 @@ extern "C" int slhip_object_crops_check_params(const slhip_object_crop_params* p
         slhip::set_error("%s: min_visib_fract %g must be in [0, 1]", who, (double)p->min_visib_fract);
         return -1;
     }
-    if (!(p->fx > 0.0f) || !(p->fy > 0.0f) || !is_finite(p->fx) || !is_finite(p->fy) || !is_finite(p->cx) || !is_finite(p->cy)) {
-        slhip::set_error("%s: intrinsics (fx %g, fy %g, cx %g, cy %g): fx and fy must be positive, all four finite", who,
-                         (double)p->fx, (double)p->fy, (double)p->cx, (double)p->cy);
-        return -1;
-    }
+    if (const int st = slhip::check_intrinsics(who, p->fx, p->fy, p->cx, p->cy)) return st;
     const uint32_t all = SLHIP_CROP_RGB | SLHIP_CROP_COORD | SLHIP_CROP_NORMALS | SLHIP_CROP_INSTANCE | SLHIP_CROP_MASK;
     if (p->outputs == 0u || (p->outputs & ~all)) {
         slhip::set_error("%s: outputs 0x%x must name at least one of rgb 1, coord 2, normals 4, instance 8, mask 16 and nothing else",
@@ -291,7 +248,7 @@ extern "C" int slhip_object_crops_scratch_bytes(uint32_t n_scenes, uint64_t* byt
         slhip::set_error("slhip_object_crops_scratch_bytes: null argument");
         return -1;
     }
-    *bytes = ((uint64_t)n_scenes + 1u) * 8u;      // per-scene counts / offsets, then the total
+    *bytes = slhip::select_scratch_bytes(n_scenes);
     return 0;
 }
 
@@ -310,29 +267,8 @@ extern "C" int slhip_object_crops_select(const slhip_object_crop_params* params,
         slhip::set_error("slhip_object_crops_select: n_slots must be at least 1 (slot 0 is the background)");
         return -1;
     }
-    *n_out = 0;
-    if (n_scenes == 0u) return 0;
-    unsigned long long* counts = (unsigned long long*)d_scratch;
-    const uint32_t blocks = (n_scenes + 3u) / 4u;
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[0], stream));
-    k_crop_count<<<blocks, 256, 0, stream>>>(*params, d_stats, n_scenes, n_slots, counts);
-    slhip::k_scan_counts<1024><<<1, 1024, 0, stream>>>(counts, n_scenes);
-    k_crop_emit<<<blocks, 256, 0, stream>>>(*params, d_stats, n_scenes, n_slots, counts, d_crops, capacity);
-    SLHIP_LAUNCH_CHECK();
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[1], stream));
-        g_timed[0] = true;
-    }
-    unsigned long long total = 0;
-    SLHIP_CHECK(hipMemcpyAsync(&total, counts + n_scenes, 8, hipMemcpyDeviceToHost, stream));
-    SLHIP_CHECK(hipStreamSynchronize(stream));
-    *n_out = total;
-    if (total > capacity) {
-        slhip::set_error("slhip_object_crops_select: d_crops holds %llu records, this batch needs %llu",
-                         (unsigned long long)capacity, total);
-        return SLHIP_OBJECT_CROPS_CAPACITY;
-    }
-    return 0;
+    return slhip::select<CropRule>(*params, n_scenes, n_slots, d_crops, capacity, d_scratch, n_out, stream, SLHIP_OBJECT_CROPS_CAPACITY,
+                                   "slhip_object_crops_select", "d_crops", g_timer, 0, d_stats);
 }
 
 extern "C" int slhip_object_crops_gather(const slhip_object_crop_params* params, const slhip_object_crop* d_crops,
@@ -380,15 +316,11 @@ extern "C" int slhip_object_crops_gather(const slhip_object_crop_params* params,
     dst.mask = out->d_mask;
     const uint32_t bpc = (params->size * params->size + 255u) / 256u;      // blocks per crop
     const uint64_t per_launch = 0x7fffffffu / bpc;                         // crops whose blocks fit the grid's x extent
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[2], stream));
+    if (const int st = g_timer.begin(1, stream)) return st;
     for (uint64_t c0 = 0; c0 < n_crops; c0 += per_launch) {
         const uint64_t n = std::min<uint64_t>(per_launch, n_crops - c0);
         k_crop_gather<<<dim3((uint32_t)(n * bpc)), 256, 0, stream>>>(*params, d_crops, c0, bpc, src, n_scenes, n_slots, W, H, dst);
     }
     SLHIP_LAUNCH_CHECK();
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[3], stream));
-        g_timed[1] = true;
-    }
-    return 0;
+    return g_timer.end(1, stream);
 }

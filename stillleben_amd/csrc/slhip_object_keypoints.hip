@@ -4,8 +4,7 @@
 // object.  include/slhip.h "Object keypoints" and DESIGN.md "Object keypoints" are the contract; all arithmetic is float32, one
 // rounded operation at a time (-ffp-contract=off), through slhip_keypoint_rules.h on host and device alike, so
 // tests/object_keypoints_ref.py restates it and every output is bit-exact against it.
-//   k_keypoints_fps      one workgroup per class: n_fps rounds of {update dmin, max value then lowest index}; the reduction goes
-//                        through the wave by shuffles, then through LDS; it does not depend on the order
+//   fps                  k_fps of slhip_fps.hip (slhip::fps_device)
 //   k_keypoints_project  one thread per (scene, object, keypoint)
 //   k_keypoints_field    a pure write stream: a scene's uv and flags in LDS, (pixel, keypoint) pairs flattened across the lanes,
 //                        two pairs = one 16-byte store per lane when a scene's pairs are even (8 bytes otherwise)
@@ -13,106 +12,26 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <vector>
 
 #include "slhip.h"
+#include "slhip_checks.h"
 #include "slhip_common.h"
+#include "slhip_fps.h"
 #include "slhip_keypoint_rules.h"
+#include "slhip_step_timer.h"
 
 namespace {
 
 static_assert(sizeof(slhip_object_keypoint_params) == 48, "slhip_object_keypoint_params layout");
-static_assert(sizeof(slhip_asset) == 224, "slhip_asset layout");
-static_assert(sizeof(slhip_draw) == 432, "slhip_draw layout");
 static_assert(sizeof(slhip_synth_object) == 16, "slhip_synth_object layout");
 
 using Params = slhip_object_keypoint_params;
 namespace kp = slhip_kp;
 
-constexpr uint32_t FPS_BLOCK = 1024u;      // one workgroup per class
-constexpr uint32_t FPS_WAVES = FPS_BLOCK / 64u;
 constexpr uint32_t FIELD_BLOCK = 256u;
 constexpr uint32_t FIELD_TRIPS = 4u;        // units a lane of k_keypoints_field has in flight
 constexpr uint32_t MAX_KP = SLHIP_KEYPOINTS_MAX;
 constexpr uint32_t MAX_SLOTS = SLHIP_SYNTH_MAX_OBJECTS * MAX_KP;      // (object, keypoint) of one scene
-
-using kp::class_vertices;
-
-__device__ __forceinline__ kp::Best wave_best(kp::Best b)
-{
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        kp::Best o;
-        o.val = __shfl_xor(b.val, d, 64);
-        o.idx = __shfl_xor(b.idx, d, 64);
-        b = kp::join(b, o);
-    }
-    return b;
-}
-
-// Block c is class c.  Thread t owns vertices t, t + FPS_BLOCK, ...: their dmin is read and written by it alone, in row c of the
-// scratch (max_verts floats).  Every read of the pool is inside [base, base + n), which class_vertices bounds by n_vertices.
-__global__ __launch_bounds__(FPS_BLOCK) void k_keypoints_fps(const float4* __restrict__ pos, uint64_t n_vertices,
-                                                             const slhip_asset* __restrict__ assets,
-                                                             const slhip_draw* __restrict__ templates, uint32_t n_templates,
-                                                             uint32_t n_fps, uint64_t max_verts, float* __restrict__ scratch,
-                                                             float4* __restrict__ keypoints, int32_t* __restrict__ vertex)
-{
-    __shared__ float s_val[2][FPS_WAVES];
-    __shared__ int s_idx[2][FPS_WAVES];
-    const uint32_t c = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const slhip_asset& a = assets[c];
-    uint64_t base;
-    uint32_t n;
-    class_vertices(a, templates, n_templates, n_vertices, max_verts, &base, &n);
-    float m2o[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) m2o[i] = a.mesh_to_object[i];
-    const kp::P3 o = kp::bbox_centre(a.bbox_min, a.bbox_max);
-    float4* kout = keypoints + (size_t)c * n_fps;
-    int32_t* vout = vertex + (size_t)c * n_fps;
-    if (n == 0u) {      // uniform over the block
-        for (uint32_t k = tid; k < n_fps; k += FPS_BLOCK) {
-            kout[k] = make_float4(o.x, o.y, o.z, 1.0f);
-            vout[k] = -1;
-        }
-        return;
-    }
-    float* dmin = scratch + (size_t)c * max_verts;
-    const float4* cp = pos + base;
-    kp::P3 last = o;      // round 0 measures from the bbox centre
-    for (uint32_t k = 0u; k < n_fps; ++k) {
-        kp::Best mine = kp::best_start();
-        for (uint32_t v = tid; v < n; v += FPS_BLOCK) {
-            const float4 q = cp[v];
-            const float d = kp::d2(kp::object_point(m2o, q.x, q.y, q.z), last);
-            const float m = k == 0u ? d : kp::keep_min(dmin[v], d);
-            dmin[v] = m;
-            mine = kp::offer(mine, m, (int)v);
-        }
-        mine = wave_best(mine);
-        if (lane == 0u) {
-            s_val[k & 1u][wave] = mine.val;
-            s_idx[k & 1u][wave] = mine.idx;
-        }
-        __syncthreads();      // (the other half of s_* is last read before the previous round's barrier is passed by all)
-        kp::Best all = kp::best_start();
-#pragma unroll
-        for (uint32_t w = 0u; w < FPS_WAVES; ++w) {
-            kp::Best b;
-            b.val = s_val[k & 1u][w];
-            b.idx = s_idx[k & 1u][w];
-            all = kp::join(all, b);
-        }
-        const int i = kp::best_index(all);      // < n: only offered indices and 0 come out
-        const float4 q = cp[i];
-        last = kp::object_point(m2o, q.x, q.y, q.z);
-        if (tid == 0u) {
-            kout[k] = make_float4(last.x, last.y, last.z, 1.0f);
-            vout[k] = i;
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void k_keypoints_project(Params p, const float4* __restrict__ bank, uint32_t n_assets,
                                                            const slhip_synth_object* __restrict__ objects,
@@ -230,33 +149,11 @@ __global__ __launch_bounds__(FIELD_BLOCK) void k_keypoints_field(Params p, const
 }
 
 // optional HIP-event timing (tools/time_object_keypoints.py): events round the last call's kernel of each of the three steps
-bool g_timing = false;
-hipEvent_t g_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-bool g_timed[3] = {false, false, false};
-
-int check_fps(const char* who, const char* what, uint32_t limit, uint32_t n_assets, uint32_t n_fps)
-{
-    if (n_assets == 0u || n_assets > SLHIP_SYNTH_MAX_ASSETS) {
-        slhip::set_error("%s: n_assets %u must be in [1, %u]", who, n_assets, SLHIP_SYNTH_MAX_ASSETS);
-        return -1;
-    }
-    if (n_fps < 1u || n_fps > limit) {
-        slhip::set_error("%s: %s %u must be in [1, %u]", who, what, n_fps, limit);
-        return -1;
-    }
-    return 0;
-}
+slhip::StepTimer<3> g_timer;
 
 }  // namespace
 
-extern "C" int slhip_object_keypoints_timing_enable(int on)
-{
-    if (on && !g_ev[0])
-        for (hipEvent_t& e : g_ev) SLHIP_CHECK(hipEventCreate(&e));
-    g_timing = on != 0;
-    g_timed[0] = g_timed[1] = g_timed[2] = false;
-    return 0;
-}
+extern "C" int slhip_object_keypoints_timing_enable(int on) { return g_timer.enable(on); }
 
 extern "C" int slhip_object_keypoints_timings(float ms_out[3])
 {
@@ -264,13 +161,7 @@ extern "C" int slhip_object_keypoints_timings(float ms_out[3])
         slhip::set_error("slhip_object_keypoints_timings: null argument");
         return -1;
     }
-    for (int i = 0; i < 3; ++i) {
-        ms_out[i] = -1.0f;      // a step that was not timed
-        if (!g_timed[i]) continue;
-        SLHIP_CHECK(hipEventSynchronize(g_ev[2 * i + 1]));
-        SLHIP_CHECK(hipEventElapsedTime(&ms_out[i], g_ev[2 * i], g_ev[2 * i + 1]));
-    }
-    return 0;
+    return std::min(g_timer.read(ms_out), 0);
 }
 
 extern "C" int slhip_object_keypoints_check_params(const slhip_object_keypoint_params* p)
@@ -280,28 +171,15 @@ extern "C" int slhip_object_keypoints_check_params(const slhip_object_keypoint_p
         slhip::set_error("%s: null parameter record", who);
         return -1;
     }
-    if (!(p->fx > 0.0f) || !(p->fy > 0.0f) || !kp::is_finite(p->fx) || !kp::is_finite(p->fy) || !kp::is_finite(p->cx) || !kp::is_finite(p->cy)) {
-        slhip::set_error("%s: intrinsics (fx %g, fy %g, cx %g, cy %g): fx and fy must be positive, all four finite", who,
-                         (double)p->fx, (double)p->fy, (double)p->cx, (double)p->cy);
-        return -1;
-    }
-    if (p->W < 1 || p->H < 1 || p->W > 32768 || p->H > 32768) {
-        slhip::set_error("%s: bad picture size %d x %d (each side 1..32768)", who, p->W, p->H);
-        return -1;
-    }
-    if (p->n_keypoints < 1u || p->n_keypoints > MAX_KP) {
-        slhip::set_error("%s: n_keypoints %u must be in [1, %u]", who, p->n_keypoints, MAX_KP);
-        return -1;
-    }
-    if (p->n_objects < 1u || p->n_objects > SLHIP_SYNTH_MAX_OBJECTS) {
-        slhip::set_error("%s: n_objects %u must be in [1, %u]", who, p->n_objects, SLHIP_SYNTH_MAX_OBJECTS);
-        return -1;
-    }
+    if (const int st = slhip::check_intrinsics(who, p->fx, p->fy, p->cx, p->cy)) return st;
+    if (const int st = slhip::check_picture_sides(who, p->W, p->H)) return st;
+    if (const int st = slhip::check_range(who, "n_keypoints", p->n_keypoints, 1u, MAX_KP)) return st;
+    if (const int st = slhip::check_range(who, "n_objects", p->n_objects, 1u, SLHIP_SYNTH_MAX_OBJECTS)) return st;
     if (p->mode != SLHIP_KEYPOINT_FIELD_OFFSET && p->mode != SLHIP_KEYPOINT_FIELD_UNIT) {
         slhip::set_error("%s: mode %u must be offset 0 or unit 1", who, p->mode);
         return -1;
     }
-    if (!(p->depth_tol >= 0.0f) || !kp::is_finite(p->depth_tol)) {
+    if (!(p->depth_tol >= 0.0f) || !slhip::is_finite(p->depth_tol)) {
         slhip::set_error("%s: depth_tol %g must be finite and >= 0 (metres)", who, (double)p->depth_tol);
         return -1;
     }
@@ -314,26 +192,7 @@ extern "C" int slhip_object_keypoints_fps_bytes(uint32_t n_assets, uint64_t max_
         slhip::set_error("slhip_object_keypoints_fps_bytes: null argument");
         return -1;
     }
-    *bytes = (uint64_t)n_assets * max_verts * 4u;      // dmin: one row of max_verts floats per class
-    return 0;
-}
-
-// The FPS of slhip_object_keypoints_fps for any count up to `limit` (slhip_object_regions_centres samples up to 255 centres by
-// the same kernel): checks, then the launch.  `what` names the count in the error text.
-int slhip::fps_device(const char* who, const char* what, uint32_t limit, const float* d_pos, uint64_t n_vertices,
-                      const slhip_asset* d_assets, uint32_t n_assets, const slhip_draw* d_templates, uint32_t n_templates,
-                      uint32_t n_fps, uint64_t max_verts, void* d_scratch, float* d_keypoints, int32_t* d_vertex, hipStream_t stream)
-{
-    if (const int st = check_fps(who, what, limit, n_assets, n_fps)) return st;
-    if (!d_assets || !d_keypoints || !d_vertex || (n_templates && !d_templates) || (n_vertices && !d_pos) ||
-        (max_verts && !d_scratch)) {
-        slhip::set_error("%s: null argument (assets, outputs, and templates / vertices / scratch unless their count is 0)", who);
-        return -1;
-    }
-    k_keypoints_fps<<<n_assets, FPS_BLOCK, 0, stream>>>(reinterpret_cast<const float4*>(d_pos), n_vertices, d_assets, d_templates,
-                                                       n_templates, n_fps, max_verts, (float*)d_scratch,
-                                                       reinterpret_cast<float4*>(d_keypoints), d_vertex);
-    SLHIP_LAUNCH_CHECK();
+    *bytes = slhip::fps_scratch_bytes(n_assets, max_verts);
     return 0;
 }
 
@@ -344,57 +203,12 @@ extern "C" int slhip_object_keypoints_fps(const float* d_pos, uint64_t n_vertice
     static const char* who = "slhip_object_keypoints_fps";
     hipStream_t stream = (hipStream_t)stream_;
     // (the checks come first: a refused call records no event)
-    if (const int st = check_fps(who, "n_fps", MAX_KP, n_assets, n_fps)) return st;
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[0], stream));
+    if (const int st = slhip::check_fps(who, "n_fps", MAX_KP, n_assets, n_fps)) return st;
+    if (const int st = g_timer.begin(0, stream)) return st;
     if (const int st = slhip::fps_device(who, "n_fps", MAX_KP, d_pos, n_vertices, d_assets, n_assets, d_templates, n_templates, n_fps,
                                          max_verts, d_scratch, d_keypoints, d_vertex, stream))
         return st;
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[1], stream));
-        g_timed[0] = true;
-    }
-    return 0;
-}
-
-int slhip::fps_host(const char* who, const char* what, uint32_t limit, const float* h_pos, uint64_t n_vertices,
-                    const slhip_asset* h_assets, uint32_t n_assets, const slhip_draw* h_templates, uint32_t n_templates,
-                    uint32_t n_fps, float* h_keypoints, int32_t* h_vertex)
-{
-    if (const int st = check_fps(who, what, limit, n_assets, n_fps)) return st;
-    if (!h_assets || !h_keypoints || !h_vertex || (n_templates && !h_templates) || (n_vertices && !h_pos)) {
-        slhip::set_error("%s: null argument", who);
-        return -1;
-    }
-    std::vector<float> dmin;
-    for (uint32_t c = 0; c < n_assets; ++c) {
-        const slhip_asset& a = h_assets[c];
-        uint64_t base;
-        uint32_t n;
-        class_vertices(a, h_templates, n_templates, n_vertices, ~0ull, &base, &n);
-        const kp::P3 o = kp::bbox_centre(a.bbox_min, a.bbox_max);
-        float* kout = h_keypoints + (size_t)c * n_fps * 4u;
-        int32_t* vout = h_vertex + (size_t)c * n_fps;
-        dmin.assign(n, 0.0f);
-        kp::P3 last = o;
-        for (uint32_t k = 0; k < n_fps; ++k) {
-            int i = -1;
-            if (n) {
-                kp::Best best = kp::best_start();
-                for (uint32_t v = 0; v < n; ++v) {
-                    const float* q = h_pos + (base + v) * 4u;
-                    const float d = kp::d2(kp::object_point(a.mesh_to_object, q[0], q[1], q[2]), last);
-                    dmin[v] = k == 0u ? d : kp::keep_min(dmin[v], d);
-                    best = kp::offer(best, dmin[v], (int)v);
-                }
-                i = kp::best_index(best);
-                const float* q = h_pos + (base + (uint32_t)i) * 4u;
-                last = kp::object_point(a.mesh_to_object, q[0], q[1], q[2]);
-            }
-            kout[4u * k] = last.x; kout[4u * k + 1u] = last.y; kout[4u * k + 2u] = last.z; kout[4u * k + 3u] = 1.0f;
-            vout[k] = i;
-        }
-    }
-    return 0;
+    return g_timer.end(0, stream);
 }
 
 extern "C" int slhip_object_keypoints_fps_host(const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets,
@@ -435,16 +249,12 @@ extern "C" int slhip_object_keypoints_project(const slhip_object_keypoint_params
         slhip::set_error("%s: %llu keypoints do not fit one launch", who, (unsigned long long)n);
         return -1;
     }
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[2], stream));
+    if (const int st = g_timer.begin(1, stream)) return st;
     k_keypoints_project<<<(uint32_t)((n + 255u) / 256u), 256, 0, stream>>>(
         *params, reinterpret_cast<const float4*>(d_bank), n_assets, d_objects, d_object_to_camera, n_scenes, d_depth, depth_stride,
         reinterpret_cast<float4*>(d_camera), reinterpret_cast<float2*>(d_uv), d_flags);
     SLHIP_LAUNCH_CHECK();
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[3], stream));
-        g_timed[1] = true;
-    }
-    return 0;
+    return g_timer.end(1, stream);
 }
 
 extern "C" int slhip_object_keypoints_field(const slhip_object_keypoint_params* params, const int16_t* d_instance,
@@ -484,15 +294,11 @@ extern "C" int slhip_object_keypoints_field(const slhip_object_keypoint_params* 
     const uint32_t per_scene = (uint32_t)std::max<uint64_t>(1u, std::min<uint64_t>(want, std::max<uint32_t>(32u, 4096u / count)));
     const dim3 grid(per_scene, count);
     const float2* uv = reinterpret_cast<const float2*>(d_uv);
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[4], stream));
+    if (const int st = g_timer.begin(2, stream)) return st;
     if (wide)
         k_keypoints_field<2><<<grid, FIELD_BLOCK, 0, stream>>>(*params, d_instance, uv, d_flags, first, reinterpret_cast<float2*>(d_out));
     else
         k_keypoints_field<1><<<grid, FIELD_BLOCK, 0, stream>>>(*params, d_instance, uv, d_flags, first, reinterpret_cast<float2*>(d_out));
     SLHIP_LAUNCH_CHECK();
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[5], stream));
-        g_timed[2] = true;
-    }
-    return 0;
+    return g_timer.end(2, stream);
 }

@@ -3,9 +3,7 @@
 // points per object.  include/slhip.h "Object points" and DESIGN.md "Object points" are the contract; the choice of the pixels is
 // integer arithmetic and the camera point float32 without fma (-ffp-contract=off), so tests/object_points_ref.py restates both
 // and every output is bit-exact against it.
-//   k_points_count   one wave per scene: the eligible slots, ballot + popcount over the slots in strides of 64
-//   k_scan_counts    (slhip_scan.h) one block: exclusive scan of the per-scene counts, the total behind them
-//   k_points_emit    the walk of k_points_count again; every eligible lane writes its record at the scene's offset + its rank
+//   select           the count / scan / emit pass of slhip_select.h under PointRule
 //   k_points_gather  one workgroup per set: popcounts of the slot's kind-1 words summed per thread over a contiguous segment,
 //                    the 256 segment prefixes in LDS, then per point a search of its rank in them and a walk of one segment
 #include <hip/hip_runtime.h>
@@ -14,9 +12,12 @@
 #include <cstdint>
 
 #include "slhip.h"
+#include "slhip_checks.h"
 #include "slhip_common.h"
 #include "slhip_mask_select.h"
-#include "slhip_scan.h"
+#include "slhip_rng.h"
+#include "slhip_select.h"
+#include "slhip_step_timer.h"
 
 namespace {
 
@@ -31,22 +32,14 @@ constexpr uint32_t MAX_SLOTS = 65536u;
 
 using Params = slhip_object_point_params;
 
-// Philox4x32-10 on host and device (slhip_rng.h is device code): the counter in place
-__host__ __device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
-
 // the four draws of points 4 q .. 4 q + 3 of (scene, slot)
 __host__ __device__ inline void point_draws(const Params& p, uint32_t scene, uint32_t slot, uint32_t q, uint32_t x[4])
 {
-    x[0] = p.scene_id_base + scene; x[1] = STREAM_POINTS; x[2] = (slot << 12) | q; x[3] = 0x51DE5EEDu;
-    philox4x32_10(x, p.seed_lo, p.seed_hi);
+    slhip::Philox ph;
+    ph.c[0] = p.scene_id_base + scene; ph.c[1] = STREAM_POINTS; ph.c[2] = (slot << 12) | q; ph.c[3] = 0x51DE5EEDu;
+    ph.k[0] = p.seed_lo; ph.k[1] = p.seed_hi;
+    for (int i = 0; i < 10; ++i) ph.round();      // block() without its unroll pragma, under which k_points_gather takes 40 VGPRs for 36
+    x[0] = ph.c[0]; x[1] = ph.c[1]; x[2] = ph.c[2]; x[3] = ph.c[3];
 }
 
 // the rank of point j of K among n visible pixels under the draw x: stratum [lo, hi) of the ranks, x picks inside it
@@ -56,50 +49,28 @@ __host__ __device__ inline uint64_t point_rank(uint32_t j, uint32_t n, uint32_t 
     return lo + (uint32_t)(((uint64_t)x * (hi - lo)) >> 32);
 }
 
-__device__ __forceinline__ bool eligible(const Params& p, const slhip_object_stats& s, const slhip_object_mask& m)
-{
-    return s.px_visib >= p.min_px && (float)s.px_visib >= p.min_visib_fract * (float)s.px_all && m.tile_box[0] <= m.tile_box[2];
-}
+// the rule of slhip_select.h: a slot with enough visible pixels, a large enough visible share and a tile box gets a set
+struct PointRule {
+    typedef slhip_object_point_set Record;
+    typedef slhip_object_point_params Params;
+    Params p;
+    const slhip_object_stats* stats;
+    const slhip_object_mask* masks;
 
-// blocks of four waves, one scene per wave; the loop bounds are the same in every lane of a wave, so every ballot sees all 64
-__global__ __launch_bounds__(256) void k_points_count(Params p, const slhip_object_stats* __restrict__ stats,
-                                                      const slhip_object_mask* __restrict__ masks, uint32_t n_scenes,
-                                                      uint32_t n_slots, unsigned long long* __restrict__ counts)
-{
-    const uint32_t scene = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (scene >= n_scenes) return;
-    const size_t row = (size_t)scene * n_slots;
-    unsigned long long n = 0ull;
-    for (uint32_t base = 1u; base < n_slots; base += 64u) {
-        const uint32_t slot = base + lane;
-        const bool ok = slot < n_slots && eligible(p, stats[row + slot], masks[row + slot]);
-        n += (unsigned long long)__popcll(__ballot(ok));
+    __device__ __forceinline__ size_t row(uint32_t scene, uint32_t n_slots) const { return (size_t)scene * n_slots; }
+    __device__ __forceinline__ bool eligible(size_t row, uint32_t slot) const
+    {
+        const slhip_object_stats& s = stats[row + slot];
+        const slhip_object_mask& m = masks[row + slot];
+        return s.px_visib >= p.min_px && (float)s.px_visib >= p.min_visib_fract * (float)s.px_all && m.tile_box[0] <= m.tile_box[2];
     }
-    if (lane == 0u) counts[scene] = n;
-}
-
-__global__ __launch_bounds__(256) void k_points_emit(Params p, const slhip_object_stats* __restrict__ stats,
-                                                     const slhip_object_mask* __restrict__ masks, uint32_t n_scenes,
-                                                     uint32_t n_slots, const unsigned long long* __restrict__ offsets,
-                                                     slhip_object_point_set* __restrict__ sets, unsigned long long capacity)
-{
-    const uint32_t scene = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    if (scene >= n_scenes) return;
-    const size_t row = (size_t)scene * n_slots;
-    unsigned long long at = offsets[scene];
-    for (uint32_t base = 1u; base < n_slots; base += 64u) {
-        const uint32_t slot = base + lane;
-        const bool ok = slot < n_slots && eligible(p, stats[row + slot], masks[row + slot]);
-        const unsigned long long votes = __ballot(ok);
-        const unsigned long long mine = at + (unsigned long long)__popcll(votes & ((1ull << lane) - 1ull));
-        if (ok && mine < capacity) {
-            slhip_object_point_set r;
-            r.scene = scene; r.slot = slot; r.n_visib = stats[row + slot].px_visib; r._pad = 0u;
-            sets[mine] = r;
-        }
-        at += (unsigned long long)__popcll(votes);
+    __device__ __forceinline__ Record make(size_t row, uint32_t scene, uint32_t slot) const
+    {
+        slhip_object_point_set r;
+        r.scene = scene; r.slot = slot; r.n_visib = stats[row + slot].px_visib; r._pad = 0u;
+        return r;
     }
-}
+};
 
 struct Source {
     const uint32_t* rgb;        // the four bytes of a pixel as one word
@@ -218,11 +189,7 @@ __global__ __launch_bounds__(256) void k_points_gather(Params p, const slhip_obj
 }
 
 // optional HIP-event timing (tools/time_object_points.py): events round the last select's kernels and the last gather's
-bool g_timing = false;
-hipEvent_t g_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-bool g_timed[2] = {false, false};
-
-bool is_finite(float v) { return v - v == 0.0f; }
+slhip::StepTimer<2> g_timer;
 
 int check_slots(const char* who, uint32_t n_slots)
 {
@@ -236,27 +203,16 @@ int check_slots(const char* who, uint32_t n_slots)
 
 }  // namespace
 
-extern "C" int slhip_object_points_timing_enable(int on)
-{
-    if (on && !g_ev[0])
-        for (hipEvent_t& e : g_ev) SLHIP_CHECK(hipEventCreate(&e));
-    g_timing = on != 0;
-    g_timed[0] = g_timed[1] = false;
-    return 0;
-}
+extern "C" int slhip_object_points_timing_enable(int on) { return g_timer.enable(on); }
 
 extern "C" int slhip_object_points_timings(float ms_out[2])
 {
-    if (!ms_out || !g_timed[0] || !g_timed[1]) {
+    if (!ms_out || !g_timer.all_timed()) {
         slhip::set_error("slhip_object_points_timings: no timed calls (slhip_object_points_timing_enable(1), then "
                          "slhip_object_points_select and slhip_object_points_gather)");
         return -1;
     }
-    SLHIP_CHECK(hipEventSynchronize(g_ev[1]));
-    SLHIP_CHECK(hipEventSynchronize(g_ev[3]));
-    SLHIP_CHECK(hipEventElapsedTime(&ms_out[0], g_ev[0], g_ev[1]));
-    SLHIP_CHECK(hipEventElapsedTime(&ms_out[1], g_ev[2], g_ev[3]));
-    return 0;
+    return std::min(g_timer.read(ms_out), 0);
 }
 
 extern "C" int slhip_object_points_check_params(const slhip_object_point_params* p, int W, int H)
@@ -266,14 +222,11 @@ extern "C" int slhip_object_points_check_params(const slhip_object_point_params*
         slhip::set_error("%s: null parameter record", who);
         return -1;
     }
-    if (W <= 0 || H <= 0 || W > 32768 || H > 32768 || (uint64_t)W * (uint64_t)H > 0x7fffffffu) {
+    if (!slhip::picture_fits(W, H, 32768, 0x7fffffffu)) {
         slhip::set_error("%s: bad picture size %d x %d (each side 1..32768: a pixel is two int16; fewer than 2^31 pixels)", who, W, H);
         return -1;
     }
-    if (p->n_points < 1u || p->n_points > (uint32_t)SLHIP_OBJECT_POINTS_MAX) {
-        slhip::set_error("%s: n_points %u must be in [1, %d]", who, p->n_points, SLHIP_OBJECT_POINTS_MAX);
-        return -1;
-    }
+    if (const int st = slhip::check_range(who, "n_points", p->n_points, 1u, SLHIP_OBJECT_POINTS_MAX)) return st;
     if (p->min_px < 1u) {
         slhip::set_error("%s: min_px %u must be at least 1", who, p->min_px);
         return -1;
@@ -282,11 +235,7 @@ extern "C" int slhip_object_points_check_params(const slhip_object_point_params*
         slhip::set_error("%s: min_visib_fract %g must be in [0, 1]", who, (double)p->min_visib_fract);
         return -1;
     }
-    if (!(p->fx > 0.0f) || !(p->fy > 0.0f) || !is_finite(p->fx) || !is_finite(p->fy) || !is_finite(p->cx) || !is_finite(p->cy)) {
-        slhip::set_error("%s: intrinsics (fx %g, fy %g, cx %g, cy %g): fx and fy must be positive, all four finite", who,
-                         (double)p->fx, (double)p->fy, (double)p->cx, (double)p->cy);
-        return -1;
-    }
+    if (const int st = slhip::check_intrinsics(who, p->fx, p->fy, p->cx, p->cy)) return st;
     const uint32_t all = SLHIP_POINTS_PIXEL | SLHIP_POINTS_CAMERA | SLHIP_POINTS_COORD | SLHIP_POINTS_NORMALS | SLHIP_POINTS_RGB;
     if (p->outputs == 0u || (p->outputs & ~all)) {
         slhip::set_error("%s: outputs 0x%x must name at least one of pixel 1, camera 2, coord 4, normals 8, rgb 16 and nothing else",
@@ -302,7 +251,7 @@ extern "C" int slhip_object_points_scratch_bytes(uint32_t n_scenes, uint64_t* by
         slhip::set_error("slhip_object_points_scratch_bytes: null argument");
         return -1;
     }
-    *bytes = ((uint64_t)n_scenes + 1u) * 8u;      // per-scene counts / offsets, then the total
+    *bytes = slhip::select_scratch_bytes(n_scenes);
     return 0;
 }
 
@@ -320,28 +269,8 @@ extern "C" int slhip_object_points_select(const slhip_object_point_params* param
         return -1;
     }
     if (const int st = check_slots(who, n_slots)) return st;
-    *n_out = 0;
-    if (n_scenes == 0u) return 0;
-    unsigned long long* counts = (unsigned long long*)d_scratch;
-    const uint32_t blocks = (n_scenes + 3u) / 4u;
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[0], stream));
-    k_points_count<<<blocks, 256, 0, stream>>>(*params, d_stats, d_masks, n_scenes, n_slots, counts);
-    slhip::k_scan_counts<1024><<<1, 1024, 0, stream>>>(counts, n_scenes);
-    k_points_emit<<<blocks, 256, 0, stream>>>(*params, d_stats, d_masks, n_scenes, n_slots, counts, d_sets, capacity);
-    SLHIP_LAUNCH_CHECK();
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[1], stream));
-        g_timed[0] = true;
-    }
-    unsigned long long total = 0;
-    SLHIP_CHECK(hipMemcpyAsync(&total, counts + n_scenes, 8, hipMemcpyDeviceToHost, stream));
-    SLHIP_CHECK(hipStreamSynchronize(stream));
-    *n_out = total;
-    if (total > capacity) {
-        slhip::set_error("%s: d_sets holds %llu records, this batch needs %llu", who, (unsigned long long)capacity, total);
-        return SLHIP_OBJECT_POINTS_CAPACITY;
-    }
-    return 0;
+    return slhip::select<PointRule>(*params, n_scenes, n_slots, d_sets, capacity, d_scratch, n_out, stream, SLHIP_OBJECT_POINTS_CAPACITY,
+                                    who, "d_sets", g_timer, 0, d_stats, d_masks);
 }
 
 extern "C" int slhip_object_points_gather(const slhip_object_point_params* params, const slhip_object_point_set* d_sets,
@@ -390,17 +319,13 @@ extern "C" int slhip_object_points_gather(const slhip_object_point_params* param
     dst.normals = reinterpret_cast<float4*>(out->d_normals);
     dst.rgb = reinterpret_cast<uint32_t*>(out->d_rgb);
     const uint64_t per_launch = 0x7fffffffu;      // sets whose blocks fit the grid's x extent
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[2], stream));
+    if (const int st = g_timer.begin(1, stream)) return st;
     for (uint64_t s0 = 0; s0 < n_sets; s0 += per_launch) {
         const uint64_t n = std::min<uint64_t>(per_launch, n_sets - s0);
         k_points_gather<<<dim3((uint32_t)n), BLOCK, 0, stream>>>(*params, d_sets, s0, src, n_scenes, n_slots, W, H, dst);
     }
     SLHIP_LAUNCH_CHECK();
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[3], stream));
-        g_timed[1] = true;
-    }
-    return 0;
+    return g_timer.end(1, stream);
 }
 
 extern "C" int slhip_object_points_host_pixels(const slhip_object_point_params* params, uint32_t scene, uint32_t slot,

@@ -5,7 +5,7 @@
 // regions" and DESIGN.md "Object regions" are the contract; all arithmetic is float32, one rounded operation at a time
 // (-ffp-contract=off), through slhip_region_rules.h on host and device alike, so tests/object_regions_ref.py restates it and
 // every output is bit-exact against it.
-//   centres              k_keypoints_fps of slhip_object_keypoints.hip with n_fps = R (slhip::fps_device)
+//   centres              k_fps of slhip_fps.hip with n_fps = R (slhip::fps_device)
 //   k_regions_vertices   blocks (x, class): one thread per vertex of the class, the class's centres at block-uniform addresses;
 //                        counts by integer adds, extents by integer maxima of the bit patterns
 //   k_regions_label      one wave per 256 consecutive bytes of `region`; a wave without object pixels writes its bytes and
@@ -13,12 +13,16 @@
 //                        addresses
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 
 #include "slhip.h"
+#include "slhip_checks.h"
 #include "slhip_common.h"
+#include "slhip_fps.h"
 #include "slhip_region_rules.h"
+#include "slhip_step_timer.h"
 
 namespace {
 
@@ -295,21 +299,11 @@ __global__ __launch_bounds__(LABEL_BLOCK) void k_regions_label(Params p, const i
 }
 
 // optional HIP-event timing (tools/time_object_regions.py): events round the last call's work of each of the three steps
-bool g_timing = false;
-hipEvent_t g_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-bool g_timed[3] = {false, false, false};
+slhip::StepTimer<3> g_timer;
 
 int check_bank(const char* who, uint32_t n_assets, uint32_t n_regions)
 {
-    if (n_assets == 0u || n_assets > SLHIP_SYNTH_MAX_ASSETS) {
-        slhip::set_error("%s: n_assets %u must be in [1, %u]", who, n_assets, SLHIP_SYNTH_MAX_ASSETS);
-        return -1;
-    }
-    if (n_regions < 1u || n_regions > MAX_R) {
-        slhip::set_error("%s: n_regions %u must be in [1, %u]", who, n_regions, MAX_R);
-        return -1;
-    }
-    return 0;
+    return slhip::check_fps(who, "n_regions", MAX_R, n_assets, n_regions);
 }
 
 int check_vertices(const char* who, const void* pos, uint64_t n_vertices, const void* assets, uint32_t n_assets, const void* templates,
@@ -358,14 +352,7 @@ int check_label(const char* who, const Params* p, const void* instance, const vo
 
 }  // namespace
 
-extern "C" int slhip_object_regions_timing_enable(int on)
-{
-    if (on && !g_ev[0])
-        for (hipEvent_t& e : g_ev) SLHIP_CHECK(hipEventCreate(&e));
-    g_timing = on != 0;
-    g_timed[0] = g_timed[1] = g_timed[2] = false;
-    return 0;
-}
+extern "C" int slhip_object_regions_timing_enable(int on) { return g_timer.enable(on); }
 
 extern "C" int slhip_object_regions_timings(float ms_out[3])
 {
@@ -373,13 +360,7 @@ extern "C" int slhip_object_regions_timings(float ms_out[3])
         slhip::set_error("slhip_object_regions_timings: null argument");
         return -1;
     }
-    for (int i = 0; i < 3; ++i) {
-        ms_out[i] = -1.0f;      // a step that was not timed
-        if (!g_timed[i]) continue;
-        SLHIP_CHECK(hipEventSynchronize(g_ev[2 * i + 1]));
-        SLHIP_CHECK(hipEventElapsedTime(&ms_out[i], g_ev[2 * i], g_ev[2 * i + 1]));
-    }
-    return 0;
+    return std::min(g_timer.read(ms_out), 0);
 }
 
 extern "C" int slhip_object_regions_check_params(const slhip_object_region_params* p)
@@ -389,26 +370,14 @@ extern "C" int slhip_object_regions_check_params(const slhip_object_region_param
         slhip::set_error("%s: null parameter record", who);
         return -1;
     }
-    if (p->W < 1 || p->H < 1 || p->W > 32768 || p->H > 32768) {
-        slhip::set_error("%s: bad picture size %d x %d (each side 1..32768)", who, p->W, p->H);
-        return -1;
-    }
+    if (const int st = slhip::check_picture_sides(who, p->W, p->H)) return st;
     if ((uint64_t)p->n_images * (uint64_t)p->W * (uint64_t)p->H >= 0xffffffffull - 2048u) {
         slhip::set_error("%s: n_images %u of %d x %d: the pixels of one call must stay below 2^32 - 2048", who, p->n_images, p->W, p->H);
         return -1;
     }
-    if (p->n_objects < 1u || p->n_objects > SLHIP_SYNTH_MAX_OBJECTS) {
-        slhip::set_error("%s: n_objects %u must be in [1, %u]", who, p->n_objects, SLHIP_SYNTH_MAX_OBJECTS);
-        return -1;
-    }
-    if (p->n_regions < 1u || p->n_regions > MAX_R) {
-        slhip::set_error("%s: n_regions %u must be in [1, %u]", who, p->n_regions, MAX_R);
-        return -1;
-    }
-    if (p->n_assets < 1u || p->n_assets > SLHIP_SYNTH_MAX_ASSETS) {
-        slhip::set_error("%s: n_assets %u must be in [1, %u]", who, p->n_assets, SLHIP_SYNTH_MAX_ASSETS);
-        return -1;
-    }
+    if (const int st = slhip::check_range(who, "n_objects", p->n_objects, 1u, SLHIP_SYNTH_MAX_OBJECTS)) return st;
+    if (const int st = slhip::check_range(who, "n_regions", p->n_regions, 1u, MAX_R)) return st;
+    if (const int st = slhip::check_range(who, "n_assets", p->n_assets, 1u, SLHIP_SYNTH_MAX_ASSETS)) return st;
     if (p->outputs & ~(SLHIP_REGIONS_OUT_LOCAL | SLHIP_REGIONS_OUT_HISTOGRAM)) {
         slhip::set_error("%s: outputs 0x%x has bits other than local 1 and histogram 2", who, p->outputs);
         return -1;
@@ -426,7 +395,7 @@ extern "C" int slhip_object_regions_centres_bytes(uint32_t n_assets, uint64_t ma
         slhip::set_error("slhip_object_regions_centres_bytes: null argument");
         return -1;
     }
-    *bytes = (uint64_t)n_assets * max_verts * 4u;      // dmin of the FPS: one row of max_verts floats per class
+    *bytes = slhip::fps_scratch_bytes(n_assets, max_verts);
     return 0;
 }
 
@@ -437,15 +406,11 @@ extern "C" int slhip_object_regions_centres(const float* d_pos, uint64_t n_verti
     static const char* who = "slhip_object_regions_centres";
     hipStream_t stream = (hipStream_t)stream_;
     if (const int st = check_bank(who, n_assets, n_regions)) return st;
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[0], stream));
+    if (const int st = g_timer.begin(0, stream)) return st;
     if (const int st = slhip::fps_device(who, "n_regions", MAX_R, d_pos, n_vertices, d_assets, n_assets, d_templates, n_templates,
                                          n_regions, max_verts, d_scratch, d_centres, d_vertex, stream))
         return st;
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[1], stream));
-        g_timed[0] = true;
-    }
-    return 0;
+    return g_timer.end(0, stream);
 }
 
 extern "C" int slhip_object_regions_centres_host(const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets,
@@ -467,7 +432,7 @@ extern "C" int slhip_object_regions_vertices(const float* d_pos, uint64_t n_vert
                                       d_vertex_region, d_count, d_extent, true))
         return st;
     const size_t slots = (size_t)n_assets * n_regions;
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[2], stream));
+    if (const int st = g_timer.begin(1, stream)) return st;
     if (n_vertices) SLHIP_CHECK(hipMemsetAsync(d_vertex_region, SLHIP_REGION_NONE, (size_t)n_vertices, stream));
     SLHIP_CHECK(hipMemsetAsync(d_count, 0, slots * 4u, stream));
     SLHIP_CHECK(hipMemsetAsync(d_extent, 0, slots * 16u, stream));
@@ -479,11 +444,7 @@ extern "C" int slhip_object_regions_vertices(const float* d_pos, uint64_t n_vert
                                                            n_regions, d_vertex_region, d_count, reinterpret_cast<uint32_t*>(d_extent));
         SLHIP_LAUNCH_CHECK();
     }
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[3], stream));
-        g_timed[1] = true;
-    }
-    return 0;
+    return g_timer.end(1, stream);
 }
 
 extern "C" int slhip_object_regions_vertices_host(const float* h_pos, uint64_t n_vertices, const slhip_asset* h_assets,
@@ -536,18 +497,14 @@ extern "C" int slhip_object_regions_label(const slhip_object_region_params* para
     const uint32_t total = params->n_images * (uint32_t)params->W * (uint32_t)params->H;      // < 2^32 - 2048
     const uint32_t mis = (uint32_t)((uintptr_t)d_region & 3u);
     const uint32_t blocks = (uint32_t)(((uint64_t)total + mis + BLOCK_BYTES - 1u) / BLOCK_BYTES);
-    if (g_timing) SLHIP_CHECK(hipEventRecord(g_ev[4], stream));
+    if (const int st = g_timer.begin(2, stream)) return st;
     if (params->outputs & SLHIP_REGIONS_OUT_HISTOGRAM)
         SLHIP_CHECK(hipMemsetAsync(d_histogram, 0, (size_t)params->n_images * params->n_objects * params->n_regions * 4u, stream));
     k_regions_label<<<blocks, LABEL_BLOCK, 0, stream>>>(*params, d_instance, reinterpret_cast<const float4*>(d_coord), d_classes,
                                                        class_stride, reinterpret_cast<const float4*>(d_centres), d_region - mis, mis,
                                                        reinterpret_cast<float4*>(d_local), d_histogram);
     SLHIP_LAUNCH_CHECK();
-    if (g_timing) {
-        SLHIP_CHECK(hipEventRecord(g_ev[5], stream));
-        g_timed[2] = true;
-    }
-    return 0;
+    return g_timer.end(2, stream);
 }
 
 extern "C" int slhip_object_regions_label_host(const slhip_object_region_params* params, const int16_t* h_instance,

@@ -1,5 +1,6 @@
 // slhip_rng.h -- counter-based RNG of the sensor models (slhip_camera.hip, slhip_depth_sensor.hip): Philox4x32-10 keyed by
-// the image's seed, counted by (pixel, image), with the uniform / normal / Poisson draws on top.  Device code only.
+// the image's seed, counted by (pixel, image), with the uniform / normal / Poisson draws on top.  Philox (also the jitter of
+// slhip_object_crops.hip and the draws of slhip_object_points.hip) runs on host and device; Rng is device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,14 +10,14 @@ namespace slhip {
 
 struct Philox {
     uint32_t c[4], k[2];
-    __device__ void round()
+    __host__ __device__ void round()
     {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
         const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1];
         c[0] = n0; c[1] = (uint32_t)p1; c[2] = n2; c[3] = (uint32_t)p0;
         k[0] += 0x9E3779B9u; k[1] += 0xBB67AE85u;
     }
-    __device__ void block()
+    __host__ __device__ void block()
     {
 #pragma unroll
         for (int i = 0; i < 10; ++i) round();

@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, _device
 
 __all__ = ["RANGE", "GRAZING", "SHADOW", "SUPPORT", "DROPOUT", "make_params", "check_params", "scratch_bytes", "process_batch",
            "process_buffers"]
@@ -113,15 +113,14 @@ def process_batch(depth, params, ndotv=None, out="float", flags=False):
     o_f = torch.empty((n, H, W), dtype=torch.float32, device=dev) if out in ("float", "both") else None
     o_u = torch.empty((n, H, W), dtype=torch.uint16, device=dev) if out in ("uint16", "both") else None
     o_g = torch.empty((n, H, W), dtype=torch.uint8, device=dev) if flags else None
-    scratch = torch.empty(max(16, scratch_bytes(n, W, H)), dtype=torch.uint8, device=dev)
+    scratch = _device.scratch(scratch_bytes(n, W, H), dev)
 
     def ptr(t):
         return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
-    stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
         st = L.slhip_depth_sensor(ptr(z), zs, ptr(c), cs, n, H, W, ptr(d_params), ptr(o_f), ptr(o_u), ptr(o_g), ptr(scratch),
-                                  C.c_void_p(stream))
+                                  _device.stream_ptr(dev))
     _abi.check(st, "slhip_depth_sensor")
     res = [t for t in (o_f, o_u, o_g) if t is not None]
     for t in res:                                   # the launch is asynchronous: its inputs live as long as its outputs

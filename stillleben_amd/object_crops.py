@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, _device, _record_set
 
 __all__ = ["OUTPUTS", "BOXES", "ObjectCrops", "make_params", "check_params", "extract"]
 
@@ -33,23 +33,13 @@ def make_params(intrinsics, size=128, box="visib", pad=1.4, jitter_scale=0.0, ji
     an integer, or the (lo, hi) pair of a Philox key."""
     if box not in BOXES:
         raise ValueError("box must be 'visib' (bbox_visib) or 'obj' (bbox_obj), not %r" % (box,))
-    if isinstance(outputs, str):
-        outputs = (outputs,)
-    bits = 0
-    for name in outputs:
-        if name not in OUTPUTS:
-            raise ValueError("outputs: unknown %r (known: %s)" % (name, ", ".join(OUTPUTS)))
-        bits |= OUTPUTS[name]
+    bits = _record_set.output_bits(outputs, OUTPUTS)
     p = np.zeros((), _abi.OBJECT_CROP_PARAMS_DTYPE)
     p["size"], p["box"] = int(size), BOXES[box]
     p["pad"], p["jitter_scale"], p["jitter_shift"] = np.float32(pad), np.float32(jitter_scale), np.float32(jitter_shift)
     p["min_px"], p["min_visib_fract"] = int(min_px), np.float32(min_visib_fract)
     p["fx"], p["fy"], p["cx"], p["cy"] = (np.float32(v) for v in intrinsics)
-    if isinstance(seed, (tuple, list)):
-        p["seed_lo"], p["seed_hi"] = int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF
-    else:
-        p["seed_lo"], p["seed_hi"] = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
-    p["scene_id_base"] = int(scene_id_base) & 0xFFFFFFFF
+    _record_set.set_key(p, seed, scene_id_base)
     p["outputs"], p["isolate"] = bits, 1 if isolate else 0
     return p
 
@@ -61,7 +51,7 @@ def check_params(params, width, height):
     return rec
 
 
-class ObjectCrops:
+class ObjectCrops(_record_set.RecordSet):
     """n windows of N x N pixels.  Tensors (None when not asked for):
         rgb       uint8 [n, N, N, 4]       coord    float32 [n, N, N, 4] (object xyz, camera z)
         normals   float32 [n, N, N, 4]     instance int16 [n, N, N]
@@ -71,20 +61,16 @@ class ObjectCrops:
         K            float32 [n, 4] = fx', fy', cx', cy' of the window; K3x3() the matrices
     SceneBatch.crops adds scene_global (int32 [n]) and, when the batch keeps it, object_to_camera (float32 [n, 3, 4])."""
 
+    _TENSORS, _ITEM = _TENSORS, "crop"
+
     def __init__(self, records, size, rgb=None, coord=None, normals=None, instance=None, mask=None, scene_global=None,
                  object_to_camera=None):
-        self.records, self.size = records, int(size)
+        super().__init__(records, scene_global, object_to_camera)
+        self.size = int(size)
         self.rgb, self.coord, self.normals, self.instance, self.mask = rgb, coord, normals, instance, mask
-        self.scene_global, self.object_to_camera = scene_global, object_to_camera
-        self._keepalive = ()
 
-    @property
-    def scene(self):
-        return self.records[..., 0]
-
-    @property
-    def slot(self):
-        return self.records[..., 1]
+    def _like(self, records):
+        return ObjectCrops(records, self.size)
 
     @property
     def box(self):
@@ -109,40 +95,10 @@ class ObjectCrops:
     def mask_all(self):
         return None if self.mask is None else (self.mask & 2) != 0
 
-    def map(self, fn):
-        """A new ObjectCrops with fn applied to every tensor (indexing, .cpu(), .clone(), ...)."""
-        out = ObjectCrops(fn(self.records), self.size)
-        for name in _TENSORS[1:]:
-            t = getattr(self, name)
-            setattr(out, name, None if t is None else fn(t))
-        out._keepalive = self._keepalive
-        return out
-
-    def __len__(self):
-        if self.records.dim() != 2:
-            raise TypeError("a single crop has no length")
-        return self.records.shape[0]
-
-    def __getitem__(self, i):
-        """Crop i (the leading dimension is dropped) or the crops of a slice."""
-        if self.records.dim() != 2:
-            raise TypeError("a single crop cannot be indexed")
-        if not isinstance(i, slice):
-            i = range(len(self))[i]
-        return self.map(lambda t: t[i])
-
     def __repr__(self):
         n = self.records.shape[0] if self.records.dim() == 2 else 1
         return "ObjectCrops(%d x %d x %d: %s)" % (n, self.size, self.size, ", ".join(
             k for k in ("rgb", "coord", "normals", "instance", "mask") if getattr(self, k) is not None))
-
-
-def _stats_records(stats):
-    """int32 [B, S, 10]: the slhip_object_stats array of an ObjectStats (assembled on its device, 40 bytes per slot)."""
-    pv, pa, bv, bo = stats.px_count_visib, stats.px_count_all, stats.bbox_visib, stats.bbox_obj
-    if pv.dim() != 2:
-        raise ValueError("object_crops: batched statistics [B, S] expected, got %s" % (tuple(pv.shape),))
-    return torch.cat([pv.unsqueeze(-1), pa.unsqueeze(-1), bv, bo], dim=-1).to(torch.int32).contiguous()
 
 
 def extract(buffers, intrinsics, size=128, box="visib", pad=1.4, jitter_scale=0.0, jitter_shift=0.0, min_px=1,
@@ -174,19 +130,12 @@ def extract(buffers, intrinsics, size=128, box="visib", pad=1.4, jitter_scale=0.
     need = [("rgb", bits & _abi.CROP_RGB), ("coord", bits & _abi.CROP_COORD), ("normals", bits & _abi.CROP_NORMALS),
             ("instance", bits & (_abi.CROP_INSTANCE | _abi.CROP_MASK)
              or (params["isolate"] and bits & (_abi.CROP_COORD | _abi.CROP_NORMALS)))]
-    for name, wanted in need:
-        if wanted and getattr(buffers, name, None) is None:
-            raise RuntimeError("object_crops: the `%s` target was not rendered, and the requested outputs read it" % name)
-    used = [getattr(buffers, name) for name, wanted in need if wanted]
+    used = _record_set.rendered("object_crops", buffers, need)
     B, H, W = (int(v) for v in used[0].shape[:3])
     rec = check_params(params, W, H)
-    d_stats = _stats_records(stats)
+    d_stats = stats.records()
     tensors = used + [d_stats] + ([masks.records, masks.words] if masks is not None else [])
-    for t in tensors:
-        if not t.is_cuda:
-            raise _abi.SlhipError("object_crops runs on the HIP device: pass cuda tensors (there is no CPU path)")
-        if t.device != used[0].device:
-            raise ValueError("object_crops: buffers, statistics and masks are on different devices")
+    dev = _device.require_cuda("object_crops", tensors, "buffers, statistics and masks")
     for name, wanted in need:
         t = getattr(buffers, name)
         if wanted and (tuple(t.shape[:3]) != (B, H, W) or not t.is_contiguous()):
@@ -198,44 +147,25 @@ def extract(buffers, intrinsics, size=128, box="visib", pad=1.4, jitter_scale=0.
                               or not masks.records.is_contiguous()):
         raise ValueError("object_crops: the masks do not belong to this picture (%s records, size %s)"
                          % (tuple(masks.records.shape), masks.size))
-    L = _abi.lib()
-    dev = used[0].device
     N = int(params["size"])
-    capacity = B * max(S - 1, 0)
-    records = torch.empty((max(capacity, 1), 12), dtype=torch.int32, device=dev)
-    nbytes = C.c_uint64(0)
-    _abi.check(L.slhip_object_crops_scratch_bytes(B, C.byref(nbytes)), "slhip_object_crops_scratch_bytes")
-    scratch = torch.empty(max(16, int(nbytes.value)), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    n_out = C.c_uint64(0)
-    with torch.cuda.device(dev):
-        st = L.slhip_object_crops_select(rec.ctypes.data, C.c_void_p(d_stats.data_ptr()), B, S, W, H,
-                                         C.c_void_p(records.data_ptr()), capacity, C.c_void_p(scratch.data_ptr()),
-                                         C.byref(n_out), C.c_void_p(stream))
-    _abi.check(st, "slhip_object_crops_select")
-    n = int(n_out.value)
-    records = records[:n]
-
-    def mk(bit, shape, dtype):
-        return torch.empty((n,) + shape, dtype=dtype, device=dev) if bits & bit else None
-
-    crops = ObjectCrops(records, N, rgb=mk(_abi.CROP_RGB, (N, N, 4), torch.uint8), coord=mk(_abi.CROP_COORD, (N, N, 4), torch.float32),
-                        normals=mk(_abi.CROP_NORMALS, (N, N, 4), torch.float32), instance=mk(_abi.CROP_INSTANCE, (N, N), torch.int16),
-                        mask=mk(_abi.CROP_MASK, (N, N), torch.uint8))
+    records, scratch = _record_set.select("slhip_object_crops_select", rec, [d_stats], B, S, (W, H), 12, dev)
+    n = len(records)
+    crops = ObjectCrops(records, N, **_record_set.empty_outputs(n, bits, dev, (
+        ("rgb", _abi.CROP_RGB, (N, N, 4), torch.uint8), ("coord", _abi.CROP_COORD, (N, N, 4), torch.float32),
+        ("normals", _abi.CROP_NORMALS, (N, N, 4), torch.float32), ("instance", _abi.CROP_INSTANCE, (N, N), torch.int16),
+        ("mask", _abi.CROP_MASK, (N, N), torch.uint8))))
     if n:
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
+        ptr = _device.ptr
         src = _abi.RenderOut()
         src.d_rgb, src.d_coord, src.d_normals, src.d_instance = (ptr(getattr(buffers, k)) for k in ("rgb", "coord", "normals", "instance"))
         out = _abi.ObjectCropsOut()
         out.d_rgb, out.d_coord, out.d_normals, out.d_instance, out.d_mask = (ptr(t) for t in (crops.rgb, crops.coord, crops.normals,
                                                                                               crops.instance, crops.mask))
         with torch.cuda.device(dev):
-            st = L.slhip_object_crops_gather(rec.ctypes.data, C.c_void_p(records.data_ptr()), n, C.byref(src), B, W, H,
+            st = _abi.lib().slhip_object_crops_gather(rec.ctypes.data, C.c_void_p(records.data_ptr()), n, C.byref(src), B, W, H,
                                              C.c_void_p(ptr(masks.records) if masks is not None else None),
                                              C.c_void_p(ptr(masks.words) if masks is not None else None), S,
-                                             C.byref(out), C.c_void_p(stream))
+                                             C.byref(out), _device.stream_ptr(dev))
         _abi.check(st, "slhip_object_crops_gather")
     crops._keepalive = (buffers, d_stats, masks, scratch)      # the gather is asynchronous: its inputs live as long as its outputs
     return crops

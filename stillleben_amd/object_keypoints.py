@@ -20,12 +20,11 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, _device
 
 __all__ = ["MODES", "KeypointBank", "ObjectKeypoints", "make_params", "check_params", "fps", "bank", "project"]
 
 MODES = {"offset": _abi.KEYPOINT_FIELD_OFFSET, "unit": _abi.KEYPOINT_FIELD_UNIT}
-_NO_CPU = "object_keypoints runs on the HIP device: pass cuda tensors (there is no CPU path)"
 
 
 def make_params(intrinsics, size, n_keypoints, n_objects, depth_tol=0.005, mode="unit"):
@@ -53,47 +52,14 @@ def check_params(params):
 def fps_host(positions, assets, templates, n):
     """slhip_object_keypoints_fps_host: the FPS rule on host arrays (positions float32 [V, 4], slhip_asset and slhip_draw
     records).  Returns (keypoints float32 [A, n, 4], vertex int32 [A, n]).  Needs no device: the CPU tests' handle."""
-    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 4)
-    assets = np.ascontiguousarray(assets, dtype=_abi.ASSET_DTYPE).reshape(-1)
-    templates = np.ascontiguousarray(templates, dtype=_abi.DRAW_DTYPE).reshape(-1)
-    A = len(assets)
-    keypoints = np.zeros((A, max(int(n), 0), 4), np.float32)
-    vertex = np.zeros((A, max(int(n), 0)), np.int32)
-    st = _abi.lib().slhip_object_keypoints_fps_host(pos.ctypes.data if len(pos) else None, len(pos), assets.ctypes.data, A,
-                                                    templates.ctypes.data if len(templates) else None, len(templates), int(n),
-                                                    keypoints.ctypes.data, vertex.ctypes.data)
-    _abi.check(st, "slhip_object_keypoints_fps_host")
-    return keypoints, vertex
+    return _device.fps_host(positions, assets, templates, n, "slhip_object_keypoints_fps_host")
 
 
 def fps(table, n):
     """Farthest point sampling of every class of an sl.AssetTable on the device: (keypoints float32 [A, n, 4] = (x, y, z, 1) in
     the object frame -- the frame of the `coord` target --, vertex int32 [A, n], the mesh vertex each one is).  The first point
     is the vertex farthest from the bbox centre; ties go to the lowest vertex index.  Asynchronous on the current stream."""
-    eng = table.eng
-    if eng is None:
-        raise _abi.SlhipError("this AssetTable was built on host pools (test helper); build it without them to use the device")
-    d_assets, d_templates = table.device()
-    eng.pool_abi()
-    d_pos = eng._pool_dev[0]
-    A = len(table)
-    max_verts = int(table.records["n_verts"].max(initial=0))
-    nbytes = C.c_uint64(0)
-    L = _abi.lib()
-    _abi.check(L.slhip_object_keypoints_fps_bytes(A, max_verts, C.byref(nbytes)), "slhip_object_keypoints_fps_bytes")
-    dev = eng.device
-    scratch = torch.empty(max(16, int(nbytes.value)), dtype=torch.uint8, device=dev)
-    keypoints = torch.empty((A, max(int(n), 0), 4), dtype=torch.float32, device=dev)
-    vertex = torch.empty((A, max(int(n), 0)), dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        st = L.slhip_object_keypoints_fps(C.c_void_p(d_pos.data_ptr()), int(eng.pool.n_vertices), C.c_void_p(d_assets.data_ptr()), A,
-                                          C.c_void_p(d_templates.data_ptr()), len(table.templates), int(n), max_verts,
-                                          C.c_void_p(scratch.data_ptr()), C.c_void_p(keypoints.data_ptr()),
-                                          C.c_void_p(vertex.data_ptr()), C.c_void_p(stream))
-    _abi.check(st, "slhip_object_keypoints_fps")
-    keypoints._keepalive = (d_pos, d_assets, d_templates, scratch)      # the launch is asynchronous
-    return keypoints, vertex
+    return _device.fps(table, n, "slhip_object_keypoints_fps", "slhip_object_keypoints_fps_bytes")
 
 
 class KeypointBank:
@@ -192,10 +158,7 @@ class ObjectKeypoints:
         W, H = int(self.params["W"]), int(self.params["H"])
         if not isinstance(instance, torch.Tensor) or instance.dtype != torch.int16:
             raise ValueError("object_keypoints: `instance` must be an int16 tensor")
-        if not instance.is_cuda or not self.uv.is_cuda:
-            raise _abi.SlhipError(_NO_CPU)
-        if instance.device != self.uv.device:
-            raise ValueError("object_keypoints: instance and keypoints are on different devices")
+        dev = _device.require_cuda("object_keypoints", (self.uv, instance), "instance and keypoints")
         if tuple(instance.shape) not in ((B, H, W), (B, H, W, 1)) or not instance.is_contiguous():
             raise ValueError("object_keypoints: `instance` must be a contiguous [%d, %d, %d] tensor" % (B, H, W))
         first, count = (0, B) if scenes is None else (int(scenes[0]), int(scenes[1]))
@@ -208,7 +171,6 @@ class ObjectKeypoints:
         p = np.array(self.params)
         p["mode"] = int(mode)
         rec = check_params(p)
-        dev = self.uv.device
         if out is None:
             out = torch.empty((count, H, W, Kp, 2), dtype=torch.float32, device=dev)
         elif out.dtype != torch.float32 or tuple(out.shape) != (count, H, W, Kp, 2) or not out.is_contiguous() or out.device != dev:
@@ -216,7 +178,7 @@ class ObjectKeypoints:
         with torch.cuda.device(dev):
             st = _abi.lib().slhip_object_keypoints_field(rec.ctypes.data, C.c_void_p(instance.data_ptr()), C.c_void_p(self.uv.data_ptr()),
                                                          C.c_void_p(self.flags.data_ptr()), B, first, count, C.c_void_p(out.data_ptr()),
-                                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                                         _device.stream_ptr(dev))
         _abi.check(st, "slhip_object_keypoints_field")
         out._keepalive = (instance, self.uv, self.flags)      # the launch is asynchronous: its inputs live as long as its output
         return out
@@ -246,13 +208,9 @@ def project(object_to_camera, objects, bank, intrinsics, size, depth=None, depth
     names = bank.names if isinstance(bank, KeypointBank) else None
     pts = bank.points if isinstance(bank, KeypointBank) else bank
     o2c = object_to_camera
-    for t in (o2c, pts, objects) + (() if depth is None else (depth,)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("object_keypoints: object_to_camera, objects, bank and depth must be torch tensors")
-        if not t.is_cuda:
-            raise _abi.SlhipError(_NO_CPU)
-        if t.device != o2c.device:
-            raise ValueError("object_keypoints: object_to_camera, objects, bank and depth are on different devices")
+    dev = _device.require_cuda("object_keypoints", (o2c, pts, objects) + (() if depth is None else (depth,)),
+                               "object_to_camera, objects, bank and depth",
+                               "object_to_camera, objects, bank and depth must be torch tensors")
     if o2c.dtype != torch.float32 or o2c.dim() != 4 or tuple(o2c.shape[2:]) != (3, 4) or not o2c.is_contiguous():
         raise ValueError("object_keypoints: object_to_camera must be a contiguous float32 [B, O, 3, 4] tensor")
     B, O = int(o2c.shape[0]), int(o2c.shape[1])
@@ -275,7 +233,6 @@ def project(object_to_camera, objects, bank, intrinsics, size, depth=None, depth
         if depth.dtype != torch.float32 or tuple(depth.shape) not in ((B, H, W), (B, H, W, 4)) or not depth.is_contiguous():
             raise ValueError("object_keypoints: `depth` must be a contiguous float32 [%d, %d, %d] plane or [.., 4] coord target" % (B, H, W))
         d_depth, stride = (depth.data_ptr(), 1) if depth.dim() == 3 else (depth.data_ptr() + 12, 4)
-    dev = o2c.device
     camera = torch.empty((B, O, Kp, 4), dtype=torch.float32, device=dev)
     uv = torch.empty((B, O, Kp, 2), dtype=torch.float32, device=dev)
     flags = torch.empty((B, O, Kp), dtype=torch.uint8, device=dev)
@@ -284,8 +241,7 @@ def project(object_to_camera, objects, bank, intrinsics, size, depth=None, depth
             st = _abi.lib().slhip_object_keypoints_project(rec.ctypes.data, C.c_void_p(pts.data_ptr()), A, C.c_void_p(d_objects.data_ptr()),
                                                            C.c_void_p(o2c.data_ptr()), B, C.c_void_p(d_depth), stride,
                                                            C.c_void_p(camera.data_ptr()), C.c_void_p(uv.data_ptr()),
-                                                           C.c_void_p(flags.data_ptr()),
-                                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                                           C.c_void_p(flags.data_ptr()), _device.stream_ptr(dev))
         _abi.check(st, "slhip_object_keypoints_project")
     out = ObjectKeypoints(camera, uv, flags, rec[0].copy(), names)
     out._keepalive = (o2c, d_objects, pts, depth)      # the projection is asynchronous: its inputs live as long as its outputs

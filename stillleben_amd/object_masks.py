@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, _device
 
 KINDS = {"all": 0, "visib": 1}
 
@@ -115,11 +115,10 @@ class ObjectMasks:
         if out.numel():
             sel = np.array([(b, i) for b in scenes for i in slots], dtype=np.uint32)
             d_sel = torch.from_numpy(sel.view(np.int32)).to(dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
             with torch.cuda.device(dev):
                 st = _abi.lib().slhip_object_masks_expand(C.c_void_p(self.records.data_ptr()), C.c_void_p(self.words.data_ptr()),
                                                           self.n_scenes, self.n_slots, W, H, k, C.c_void_p(d_sel.data_ptr()),
-                                                          len(sel), C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+                                                          len(sel), C.c_void_p(out.data_ptr()), _device.stream_ptr(dev))
             _abi.check(st, "slhip_object_masks_expand")
         out = out.view(torch.bool)
         return out[0] if self._single else out

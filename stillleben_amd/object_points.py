@@ -18,8 +18,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _abi
-from .object_crops import _stats_records
+from . import _abi, _device, _record_set
 
 __all__ = ["OUTPUTS", "ObjectPoints", "make_params", "check_params", "extract"]
 
@@ -32,21 +31,11 @@ def make_params(intrinsics, n_points=1024, min_px=1, min_visib_fract=0.0, output
                 scene_id_base=0):
     """One slhip_object_point_params record (numpy).  `intrinsics`: (fx, fy, cx, cy) the picture was rendered with.  `seed`:
     an integer, or the (lo, hi) pair of a Philox key."""
-    if isinstance(outputs, str):
-        outputs = (outputs,)
-    bits = 0
-    for name in outputs:
-        if name not in OUTPUTS:
-            raise ValueError("outputs: unknown %r (known: %s)" % (name, ", ".join(OUTPUTS)))
-        bits |= OUTPUTS[name]
+    bits = _record_set.output_bits(outputs, OUTPUTS)
     p = np.zeros((), _abi.OBJECT_POINT_PARAMS_DTYPE)
     p["n_points"], p["min_px"], p["min_visib_fract"] = int(n_points), int(min_px), np.float32(min_visib_fract)
     p["fx"], p["fy"], p["cx"], p["cy"] = (np.float32(v) for v in intrinsics)
-    if isinstance(seed, (tuple, list)):
-        p["seed_lo"], p["seed_hi"] = int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF
-    else:
-        p["seed_lo"], p["seed_hi"] = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
-    p["scene_id_base"] = int(scene_id_base) & 0xFFFFFFFF
+    _record_set.set_key(p, seed, scene_id_base)
     p["outputs"] = bits
     return p
 
@@ -58,7 +47,7 @@ def check_params(params, width, height):
     return rec
 
 
-class ObjectPoints:
+class ObjectPoints(_record_set.RecordSet):
     """n sets of K points.  Tensors (None when not asked for):
         pixel    int16 [n, K, 2] (x, y)          camera   float32 [n, K, 4] (X, Y, Z, valid), the renderer's camera frame
         coord    float32 [n, K, 4] (object xyz, camera z)                   normals  float32 [n, K, 4]
@@ -68,20 +57,16 @@ class ObjectPoints:
         index    int64 [n, K]: y * W + x, the "choose" of DenseFusion
     SceneBatch.points adds scene_global (int32 [n]) and, when the batch keeps it, object_to_camera (float32 [n, 3, 4])."""
 
+    _TENSORS, _ITEM = _TENSORS, "set"
+
     def __init__(self, records, width, pixel=None, camera=None, coord=None, normals=None, rgb=None, scene_global=None,
                  object_to_camera=None):
-        self.records, self.width = records, int(width)
+        super().__init__(records, scene_global, object_to_camera)
+        self.width = int(width)
         self.pixel, self.camera, self.coord, self.normals, self.rgb = pixel, camera, coord, normals, rgb
-        self.scene_global, self.object_to_camera = scene_global, object_to_camera
-        self._keepalive = ()
 
-    @property
-    def scene(self):
-        return self.records[..., 0]
-
-    @property
-    def slot(self):
-        return self.records[..., 1]
+    def _like(self, records):
+        return ObjectPoints(records, self.width)
 
     @property
     def n_visib(self):
@@ -94,28 +79,6 @@ class ObjectPoints:
     @property
     def index(self):
         return None if self.pixel is None else self.pixel[..., 1].long() * self.width + self.pixel[..., 0].long()
-
-    def map(self, fn):
-        """A new ObjectPoints with fn applied to every tensor (indexing, .cpu(), .clone(), ...)."""
-        out = ObjectPoints(fn(self.records), self.width)
-        for name in _TENSORS[1:]:
-            t = getattr(self, name)
-            setattr(out, name, None if t is None else fn(t))
-        out._keepalive = self._keepalive
-        return out
-
-    def __len__(self):
-        if self.records.dim() != 2:
-            raise TypeError("a single set has no length")
-        return self.records.shape[0]
-
-    def __getitem__(self, i):
-        """Set i (the leading dimension is dropped) or the sets of a slice."""
-        if self.records.dim() != 2:
-            raise TypeError("a single set cannot be indexed")
-        if not isinstance(i, slice):
-            i = range(len(self))[i]
-        return self.map(lambda t: t[i])
 
     def __repr__(self):
         n = self.records.shape[0] if self.records.dim() == 2 else 1
@@ -151,58 +114,32 @@ def extract(buffers, intrinsics, n_points=1024, min_px=1, min_visib_fract=0.0, o
     bits = int(params["outputs"])
     need = [("coord", bits & _abi.POINTS_COORD or (bits & _abi.POINTS_CAMERA and depth is None)),
             ("normals", bits & _abi.POINTS_NORMALS), ("rgb", bits & _abi.POINTS_RGB)]
-    for name, wanted in need:
-        if wanted and getattr(buffers, name, None) is None:
-            raise RuntimeError("object_points: the `%s` target was not rendered, and the requested outputs read it" % name)
+    used = _record_set.rendered("object_points", buffers, need)
     H, W = masks.size
     B, S = (int(v) for v in masks.records.shape[:2])
     rec = check_params(params, W, H)
-    d_stats = _stats_records(stats)
-    used = [getattr(buffers, name) for name, wanted in need if wanted]
+    d_stats = stats.records()
     if bits & _abi.POINTS_CAMERA and depth is not None:
         if depth.dtype != torch.float32 or tuple(depth.shape) != (B, H, W) or not depth.is_contiguous():
             raise ValueError("object_points: `depth` must be a contiguous float32 [%d, %d, %d] tensor" % (B, H, W))
         used.append(depth)
     tensors = [masks.records, masks.words, d_stats] + used
-    for t in tensors:
-        if not t.is_cuda:
-            raise _abi.SlhipError("object_points runs on the HIP device: pass cuda tensors (there is no CPU path)")
-        if t.device != tensors[0].device:
-            raise ValueError("object_points: buffers, depth, statistics and masks are on different devices")
+    dev = _device.require_cuda("object_points", tensors, "buffers, depth, statistics and masks")
     for name, wanted in need:
         t = getattr(buffers, name)
         if wanted and (tuple(t.shape) != (B, H, W, 4) or not t.is_contiguous()):
             raise ValueError("object_points: `%s` must be a contiguous [%d, %d, %d, 4] tensor" % (name, B, H, W))
     if tuple(d_stats.shape[:2]) != (B, S) or not masks.records.is_contiguous():
         raise ValueError("object_points: statistics of %s (scenes, slots) for masks of %s" % (tuple(d_stats.shape[:2]), (B, S)))
-    L = _abi.lib()
-    dev = tensors[0].device
     K = int(params["n_points"])
-    capacity = B * max(S - 1, 0)
-    records = torch.empty((max(capacity, 1), 4), dtype=torch.int32, device=dev)
-    nbytes = C.c_uint64(0)
-    _abi.check(L.slhip_object_points_scratch_bytes(B, C.byref(nbytes)), "slhip_object_points_scratch_bytes")
-    scratch = torch.empty(max(16, int(nbytes.value)), dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    n_out = C.c_uint64(0)
-    with torch.cuda.device(dev):
-        st = L.slhip_object_points_select(rec.ctypes.data, C.c_void_p(d_stats.data_ptr()), C.c_void_p(masks.records.data_ptr()), B, S,
-                                          C.c_void_p(records.data_ptr()), capacity, C.c_void_p(scratch.data_ptr()),
-                                          C.byref(n_out), C.c_void_p(stream))
-    _abi.check(st, "slhip_object_points_select")
-    n = int(n_out.value)
-    records = records[:n]
-
-    def mk(bit, shape, dtype):
-        return torch.empty((n,) + shape, dtype=dtype, device=dev) if bits & bit else None
-
-    points = ObjectPoints(records, W, pixel=mk(_abi.POINTS_PIXEL, (K, 2), torch.int16), camera=mk(_abi.POINTS_CAMERA, (K, 4), torch.float32),
-                          coord=mk(_abi.POINTS_COORD, (K, 4), torch.float32), normals=mk(_abi.POINTS_NORMALS, (K, 4), torch.float32),
-                          rgb=mk(_abi.POINTS_RGB, (K, 4), torch.uint8))
+    records, scratch = _record_set.select("slhip_object_points_select", rec, [d_stats, masks.records], B, S, (), 4, dev)
+    n = len(records)
+    points = ObjectPoints(records, W, **_record_set.empty_outputs(n, bits, dev, (
+        ("pixel", _abi.POINTS_PIXEL, (K, 2), torch.int16), ("camera", _abi.POINTS_CAMERA, (K, 4), torch.float32),
+        ("coord", _abi.POINTS_COORD, (K, 4), torch.float32), ("normals", _abi.POINTS_NORMALS, (K, 4), torch.float32),
+        ("rgb", _abi.POINTS_RGB, (K, 4), torch.uint8))))
     if n:
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
+        ptr = _device.ptr
         src = _abi.RenderOut()
         src.d_rgb, src.d_coord, src.d_normals = (ptr(getattr(buffers, k, None)) for k in ("rgb", "coord", "normals"))
         d_depth, stride = None, 0
@@ -212,9 +149,9 @@ def extract(buffers, intrinsics, n_points=1024, min_px=1, min_visib_fract=0.0, o
         out.d_pixel, out.d_camera, out.d_coord, out.d_normals, out.d_rgb = (ptr(t) for t in (points.pixel, points.camera, points.coord,
                                                                                               points.normals, points.rgb))
         with torch.cuda.device(dev):
-            st = L.slhip_object_points_gather(rec.ctypes.data, C.c_void_p(records.data_ptr()), n, C.byref(src), C.c_void_p(d_depth),
+            st = _abi.lib().slhip_object_points_gather(rec.ctypes.data, C.c_void_p(records.data_ptr()), n, C.byref(src), C.c_void_p(d_depth),
                                               stride, B, W, H, C.c_void_p(masks.records.data_ptr()),
-                                              C.c_void_p(masks.words.data_ptr()), S, C.byref(out), C.c_void_p(stream))
+                                              C.c_void_p(masks.words.data_ptr()), S, C.byref(out), _device.stream_ptr(dev))
         _abi.check(st, "slhip_object_points_gather")
     points._keepalive = (buffers, depth, d_stats, masks, scratch)      # the gather is asynchronous: its inputs live as long as its outputs
     return points

@@ -21,13 +21,12 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, _device
 
 __all__ = ["NONE", "RegionBank", "ObjectRegions", "make_params", "check_params", "centres", "vertices", "bank", "label",
            "centres_host", "vertices_host", "label_host"]
 
 NONE = _abi.REGION_NONE
-_NO_CPU = "object_regions runs on the HIP device: pass cuda tensors (there is no CPU path)"
 
 
 def make_params(size, n_images, n_objects, n_regions, n_assets, local=False, histogram=False):
@@ -47,29 +46,15 @@ def check_params(params):
 
 
 # ---- host twins: the CPU tests' handles ----------------------------------------------------------------------------------------
-def _host_table(positions, assets, templates):
-    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 4)
-    assets = np.ascontiguousarray(assets, dtype=_abi.ASSET_DTYPE).reshape(-1)
-    templates = np.ascontiguousarray(templates, dtype=_abi.DRAW_DTYPE).reshape(-1)
-    return pos, assets, templates
-
-
 def centres_host(positions, assets, templates, n_regions):
     """slhip_object_regions_centres_host: (centres float32 [A, R, 4], vertex int32 [A, R]) on host arrays.  Needs no device."""
-    pos, assets, templates = _host_table(positions, assets, templates)
-    A, R = len(assets), max(int(n_regions), 0)
-    out, vertex = np.zeros((A, R, 4), np.float32), np.zeros((A, R), np.int32)
-    st = _abi.lib().slhip_object_regions_centres_host(pos.ctypes.data if len(pos) else None, len(pos), assets.ctypes.data, A,
-                                                      templates.ctypes.data if len(templates) else None, len(templates),
-                                                      int(n_regions), out.ctypes.data, vertex.ctypes.data)
-    _abi.check(st, "slhip_object_regions_centres_host")
-    return out, vertex
+    return _device.fps_host(positions, assets, templates, n_regions, "slhip_object_regions_centres_host")
 
 
 def vertices_host(positions, assets, templates, centres):
     """slhip_object_regions_vertices_host: (vertex_region uint8 [V], count int32 [A, R], extent float32 [A, R, 4]) on host
     arrays.  Needs no device."""
-    pos, assets, templates = _host_table(positions, assets, templates)
+    pos, assets, templates = _device.host_table(positions, assets, templates)
     cen = np.ascontiguousarray(centres, dtype=np.float32)
     A, R = len(assets), int(cen.shape[1])
     if cen.shape != (A, R, 4):
@@ -107,38 +92,12 @@ def label_host(instance, coord, classes, centres, local=False, histogram=False, 
 
 
 # ---- the bank, once per asset table --------------------------------------------------------------------------------------------
-def _table_on_device(table):
-    eng = table.eng
-    if eng is None:
-        raise _abi.SlhipError("this AssetTable was built on host pools (test helper); build it without them to use the device")
-    d_assets, d_templates = table.device()
-    eng.pool_abi()
-    return eng, eng._pool_dev[0], d_assets, d_templates
-
-
 def centres(table, n_regions):
     """Farthest point sampling of `n_regions` (1..255) centres of every class of an sl.AssetTable on the device, by the rule of
     sl.object_keypoints.fps: (centres float32 [A, R, 4] = (x, y, z, 1) in the object frame -- the frame of the `coord` target --,
     vertex int32 [A, R], the mesh vertex each one is).  The first 32 are the keypoint FPS, bit for bit.  Asynchronous on the
     current stream."""
-    eng, d_pos, d_assets, d_templates = _table_on_device(table)
-    A, R = len(table), max(int(n_regions), 0)
-    max_verts = int(table.records["n_verts"].max(initial=0))
-    nbytes = C.c_uint64(0)
-    L = _abi.lib()
-    _abi.check(L.slhip_object_regions_centres_bytes(A, max_verts, C.byref(nbytes)), "slhip_object_regions_centres_bytes")
-    dev = eng.device
-    scratch = torch.empty(max(16, int(nbytes.value)), dtype=torch.uint8, device=dev)
-    out = torch.empty((A, R, 4), dtype=torch.float32, device=dev)
-    vertex = torch.empty((A, R), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        st = L.slhip_object_regions_centres(C.c_void_p(d_pos.data_ptr()), int(eng.pool.n_vertices), C.c_void_p(d_assets.data_ptr()), A,
-                                            C.c_void_p(d_templates.data_ptr()), len(table.templates), int(n_regions), max_verts,
-                                            C.c_void_p(scratch.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(vertex.data_ptr()),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    _abi.check(st, "slhip_object_regions_centres")
-    out._keepalive = (d_pos, d_assets, d_templates, scratch)      # the launch is asynchronous
-    return out, vertex
+    return _device.fps(table, n_regions, "slhip_object_regions_centres", "slhip_object_regions_centres_bytes")
 
 
 def vertices(table, centres):
@@ -146,13 +105,12 @@ def vertices(table, centres):
     (vertex_region uint8 [n_vertices], 255 for a vertex of no class; count int32 [A, R]; extent float32 [A, R, 4] = the largest
     |dx|, |dy|, |dz| and d2 of the region's vertices against its centre, zeros for an empty region -- what EPOS normalises
     fragment coordinates by).  Asynchronous on the current stream."""
-    eng, d_pos, d_assets, d_templates = _table_on_device(table)
+    eng, d_pos, d_assets, d_templates = _device.table_on_device(table)
     dev = eng.device
     A = len(table)
-    if not isinstance(centres, torch.Tensor) or not centres.is_cuda:
-        raise _abi.SlhipError(_NO_CPU)
-    if centres.device != dev:
-        raise ValueError("object_regions: the centres and the asset table are on different devices")
+    if not isinstance(centres, torch.Tensor):
+        raise _abi.SlhipError(_device.no_cpu("object_regions"))
+    _device.require_cuda("object_regions", (centres,), "the centres and the asset table", device=dev)
     if centres.dtype != torch.float32 or centres.dim() != 3 or tuple(centres.shape[::2]) != (A, 4) or not centres.is_contiguous():
         raise ValueError("object_regions: the centres must be a contiguous float32 [%d, R, 4] tensor" % A)
     R, V = int(centres.shape[1]), int(eng.pool.n_vertices)
@@ -164,7 +122,7 @@ def vertices(table, centres):
                                                       C.c_void_p(d_templates.data_ptr()), len(table.templates),
                                                       C.c_void_p(centres.data_ptr()), R, C.c_void_p(vr.data_ptr()),
                                                       C.c_void_p(count.data_ptr()), C.c_void_p(extent.data_ptr()),
-                                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                                      _device.stream_ptr(dev))
     _abi.check(st, "slhip_object_regions_vertices")
     vr._keepalive = (d_pos, d_assets, d_templates, centres)      # the launch is asynchronous
     return vr, count, extent
@@ -231,33 +189,10 @@ class ObjectRegions:
         if crops.instance is None or crops.coord is None:
             raise RuntimeError("of_crops needs the crops' instance and coord outputs")
         if isinstance(classes, torch.Tensor) and classes.dtype == torch.uint8 and n_objects:
-            size = _abi.SYNTH_OBJECT_DTYPE.itemsize
-            whole = classes.numel() // (int(n_objects) * size) * int(n_objects) * size
-            classes = classes[:whole].view(torch.int32).view(-1, int(n_objects), size // 4)[..., 0]
+            classes = _device.class_tensor(classes, n_objects)
         if not isinstance(classes, torch.Tensor) or classes.dtype != torch.int32 or classes.dim() != 2:
             raise ValueError("object_regions: of_crops takes the classes as an int32 [B, O] tensor (or uint8 records and n_objects)")
         return label(crops.instance, crops.coord, classes[crops.scene.long()].contiguous(), bank, local=local, histogram=histogram)
-
-
-def _classes(classes, N, dev, n_objects):
-    """(tensor to keep, int32 pointer, stride in int32 units, O) of the `classes` argument of label()"""
-    if not isinstance(classes, torch.Tensor):
-        raise ValueError("object_regions: `classes` must be a torch tensor")
-    if not classes.is_cuda:
-        raise _abi.SlhipError(_NO_CPU)
-    if classes.device != dev:
-        raise ValueError("object_regions: instance and classes are on different devices")
-    if classes.dtype == torch.uint8:      # slhip_synth_object records: .asset is their first word
-        size = _abi.SYNTH_OBJECT_DTYPE.itemsize
-        if n_objects is None or int(n_objects) < 1:
-            raise ValueError("object_regions: object records need n_objects")
-        O = int(n_objects)
-        if classes.dim() != 1 or classes.numel() < N * O * size or not classes.is_contiguous() or classes.data_ptr() % 4:
-            raise ValueError("object_regions: the object records must hold %d x %d slhip_synth_object" % (N, O))
-        return classes, classes.data_ptr(), size // 4, O
-    if classes.dtype != torch.int32 or classes.dim() != 2 or classes.shape[0] != N or not classes.is_contiguous():
-        raise ValueError("object_regions: `classes` must be a contiguous int32 [%d, O] tensor (or uint8 object records)" % N)
-    return classes, classes.data_ptr(), 1, int(classes.shape[1])
 
 
 def label(instance, coord, classes, bank, local=False, histogram=False, n_objects=None):
@@ -272,14 +207,8 @@ def label(instance, coord, classes, bank, local=False, histogram=False, n_object
 
     Asynchronous on the current stream."""
     cen = bank.centres if isinstance(bank, RegionBank) else bank
-    for t in (instance, coord, cen):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("object_regions: instance, coord, classes and the bank must be torch tensors")
-        if not t.is_cuda:
-            raise _abi.SlhipError(_NO_CPU)
-        if t.device != instance.device:
-            raise ValueError("object_regions: instance, coord and the bank are on different devices")
-    dev = instance.device
+    dev = _device.require_cuda("object_regions", (instance, coord, cen), "instance, coord and the bank",
+                               "instance, coord, classes and the bank must be torch tensors")
     if instance.dtype != torch.int16 or instance.dim() not in (3, 4) or (instance.dim() == 4 and instance.shape[3] != 1) \
             or not instance.is_contiguous():
         raise ValueError("object_regions: `instance` must be a contiguous int16 [N, H, W] tensor")
@@ -289,7 +218,7 @@ def label(instance, coord, classes, bank, local=False, histogram=False, n_object
     if cen.dtype != torch.float32 or cen.dim() != 3 or cen.shape[2] != 4 or not cen.is_contiguous():
         raise ValueError("object_regions: the bank must be a contiguous float32 [A, R, 4] tensor")
     A, R = int(cen.shape[0]), int(cen.shape[1])
-    keep, p_classes, stride, O = _classes(classes, N, dev, n_objects)
+    keep, p_classes, stride, O = _device.object_classes("object_regions", classes, N, dev, n_objects)
     rec = check_params(make_params((W, H), N, O, R, A, local, histogram))
     region = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
     loc = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev) if local else None
@@ -299,8 +228,7 @@ def label(instance, coord, classes, bank, local=False, histogram=False, n_object
             st = _abi.lib().slhip_object_regions_label(rec.ctypes.data, C.c_void_p(instance.data_ptr()), C.c_void_p(coord.data_ptr()),
                                                        C.c_void_p(p_classes), stride, C.c_void_p(cen.data_ptr()),
                                                        C.c_void_p(region.data_ptr()), C.c_void_p(loc.data_ptr() if local else None),
-                                                       C.c_void_p(hist.data_ptr() if histogram else None),
-                                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                                       C.c_void_p(hist.data_ptr() if histogram else None), _device.stream_ptr(dev))
         _abi.check(st, "slhip_object_regions_label")
     out = ObjectRegions(region, loc, hist, rec[0].copy())
     out._keepalive = (instance, coord, keep, cen)      # the launch is asynchronous: its inputs live as long as its outputs

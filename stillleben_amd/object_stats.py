@@ -34,6 +34,13 @@ class ObjectStats:
         """From the int32 [B, S, 10] view of slhip_object_stats records (px_visib, px_all, bbox_visib[4], bbox_obj[4])."""
         return cls(rec[..., 0], rec[..., 1], rec[..., 2:6], rec[..., 6:10])
 
+    def records(self):
+        """int32 [B, S, 10]: the slhip_object_stats array of batched statistics (assembled on their device, 40 bytes per slot)."""
+        pv, pa, bv, bo = self.px_count_visib, self.px_count_all, self.bbox_visib, self.bbox_obj
+        if pv.dim() != 2:
+            raise ValueError("object_crops: batched statistics [B, S] expected, got %s" % (tuple(pv.shape),))
+        return torch.cat([pv.unsqueeze(-1), pa.unsqueeze(-1), bv, bo], dim=-1).to(torch.int32).contiguous()
+
     @property
     def n_slots(self):
         return self.px_count_all.shape[-1]

@@ -432,6 +432,28 @@ class SceneBatch:
         W, H = (float(v) for v in self.resolution)
         return (P[0, 0] * W / 2.0, P[1, 1] * H / 2.0, (P[0, 2] + 1.0) * W / 2.0, (P[1, 2] + 1.0) * H / 2.0)
 
+    def _chunk_range(self, chunk, held=None):
+        """(first scene, scenes) of render chunk `chunk`.  `held`: the scenes that a caller's buffers hold, which must cover it."""
+        s0 = int(chunk) * self.render_chunk
+        B = min(self.render_chunk, self.n_scenes - s0)
+        if B <= 0 or (held is not None and held < B):
+            raise IndexError("render chunk %d out of range%s" % (chunk, ", or `buffers` holds fewer scenes than it" if held is not None else ""))
+        return s0, B
+
+    def _extract(self, what, extract, buffers, chunk, kw):
+        """`extract` (sl.object_crops.extract, sl.object_points.extract) with the batch's intrinsics, the chunk's scene ids and
+        the key of the view last placed; scene_global and object_to_camera attached to the result"""
+        for name in ("intrinsics", "seed", "scene_id_base"):
+            if name in kw:
+                raise TypeError("SceneBatch.%s sets `%s` itself" % (what, name))
+        s0 = int(chunk) * self.render_chunk
+        key = _abi.view_key(int(self.params["seed_lo"]), int(self.params["seed_hi"]), self.view)
+        out = extract(buffers, self.intrinsics(), seed=key, scene_id_base=int(self.params["scene_id_base"]) + s0, **kw)
+        out.scene_global = out.scene + s0
+        if self.object_to_camera is not None:
+            out.object_to_camera = self.object_to_camera[out.scene_global.long(), (out.slot - 1).long()]
+        return out
+
     def crops(self, buffers, chunk=0, **kw):
         """sl.object_crops.extract on the render of chunk `chunk` (`buffers` = what render(chunk, object_stats=True) or
         render(chunk, object_masks=True) returned) with the batch's intrinsics, the scene ids of the chunk and the Philox key
@@ -440,16 +462,7 @@ class SceneBatch:
         crop's object.  `kw`: the other arguments of extract (size, box, pad, jitter_scale, jitter_shift, ...)."""
         from . import object_crops
 
-        for name in ("intrinsics", "seed", "scene_id_base"):
-            if name in kw:
-                raise TypeError("SceneBatch.crops sets `%s` itself" % name)
-        s0 = int(chunk) * self.render_chunk
-        key = _abi.view_key(int(self.params["seed_lo"]), int(self.params["seed_hi"]), self.view)
-        out = object_crops.extract(buffers, self.intrinsics(), seed=key, scene_id_base=int(self.params["scene_id_base"]) + s0, **kw)
-        out.scene_global = out.scene + s0
-        if self.object_to_camera is not None:
-            out.object_to_camera = self.object_to_camera[out.scene_global.long(), (out.slot - 1).long()]
-        return out
+        return self._extract("crops", object_crops.extract, buffers, chunk, kw)
 
     def points(self, buffers, chunk=0, **kw):
         """sl.object_points.extract on the render of chunk `chunk` (`buffers` = what render(chunk, object_masks=True) returned)
@@ -459,16 +472,7 @@ class SceneBatch:
         of extract (n_points, min_px, min_visib_fract, outputs, depth)."""
         from . import object_points
 
-        for name in ("intrinsics", "seed", "scene_id_base"):
-            if name in kw:
-                raise TypeError("SceneBatch.points sets `%s` itself" % name)
-        s0 = int(chunk) * self.render_chunk
-        key = _abi.view_key(int(self.params["seed_lo"]), int(self.params["seed_hi"]), self.view)
-        out = object_points.extract(buffers, self.intrinsics(), seed=key, scene_id_base=int(self.params["scene_id_base"]) + s0, **kw)
-        out.scene_global = out.scene + s0
-        if self.object_to_camera is not None:
-            out.object_to_camera = self.object_to_camera[out.scene_global.long(), (out.slot - 1).long()]
-        return out
+        return self._extract("points", object_points.extract, buffers, chunk, kw)
 
     def keypoints(self, buffers, chunk=0, bank=None, depth=None, **kw):
         """sl.object_keypoints.project for the render of chunk `chunk` (`buffers` = what render(chunk, ...) returned; only its
@@ -487,11 +491,7 @@ class SceneBatch:
         if self.object_to_camera is None or not self._object_to_camera_placed:
             raise RuntimeError("SceneBatch.keypoints needs object_to_camera of the view last placed: call "
                                "place(object_to_camera=True) (the last place() did not keep it)")
-        rc = self.render_chunk
-        s0 = int(chunk) * rc
-        B = min(rc, self.n_scenes - s0)
-        if B <= 0:
-            raise IndexError("render chunk %d out of range" % chunk)
+        s0, B = self._chunk_range(chunk)
         if depth is True:
             depth = buffers.coord
             if depth is None:
@@ -516,11 +516,7 @@ class SceneBatch:
             raise TypeError("SceneBatch.regions needs a bank (sl.object_regions.bank(table, ...))")
         if buffers.instance is None or buffers.coord is None:
             raise RuntimeError("object_regions: the `instance` and `coord` targets were not rendered")
-        rc = self.render_chunk
-        s0 = int(chunk) * rc
-        B = min(rc, self.n_scenes - s0)
-        if B <= 0 or int(buffers.instance.shape[0]) < B:
-            raise IndexError("render chunk %d out of range, or `buffers` holds fewer scenes than it" % chunk)
+        s0, B = self._chunk_range(chunk, int(buffers.instance.shape[0]))
         nb = self.n_objects * _abi.SYNTH_OBJECT_DTYPE.itemsize
         return object_regions.label(buffers.instance[:B], buffers.coord[:B], self.d_objects[s0 * nb:(s0 + B) * nb], bank,
                                     n_objects=self.n_objects, **kw)

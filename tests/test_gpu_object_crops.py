@@ -206,8 +206,8 @@ def tiny_buffers(stats, dev):
     return device_buffers({"instance": rng.integers(0, 3, (B, 8, 8)).astype(np.uint16), "stats": stats}, dev)
 
 
-def select_only(stats, dev, capacity=None, **kw):
-    """slhip_object_crops_select alone: (status, n_out, records on the host)"""
+def select_only(stats, dev, capacity=None, null_records=False, **kw):
+    """slhip_object_crops_select alone: (status, n_out, records on the host); `null_records`: no record array at all"""
     B, S = stats.shape
     p = oc.make_params(K, **kw).reshape(1)
     d_stats = torch.from_numpy(stats.view(np.int32).reshape(B, S, 10).copy()).to(dev)
@@ -216,8 +216,8 @@ def select_only(stats, dev, capacity=None, **kw):
     scratch = torch.empty((B + 1) * 8, dtype=torch.uint8, device=dev)
     n = C.c_uint64(0)
     with torch.cuda.device(dev):
-        st = _abi.lib().slhip_object_crops_select(p.ctypes.data, C.c_void_p(d_stats.data_ptr()), B, S, 8, 8, C.c_void_p(out.data_ptr()),
-                                                  cap, C.c_void_p(scratch.data_ptr()), C.byref(n),
+        st = _abi.lib().slhip_object_crops_select(p.ctypes.data, C.c_void_p(d_stats.data_ptr()), B, S, 8, 8,
+                                                  C.c_void_p(None if null_records else out.data_ptr()), cap, C.c_void_p(scratch.data_ptr()), C.byref(n),
                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     return st, int(n.value), out.cpu().numpy()
 
@@ -279,6 +279,62 @@ def test_selection_thresholds_empty_input_and_capacity(dev):
     assert st == 0 and n == 5
 
 
+@pytest.mark.parametrize("S", [66, 130])
+def test_selection_ragged_trips_capacity_and_no_array(dev, S):
+    """The shared select pass under the crops' rule, through the raw entry: five scenes -- the second block has one live wave
+    and three that leave at once -- of 66 and 130 slots, a ragged second and third trip of 64, about half the slots eligible
+    (the others fail min_px or hold nothing); then a capacity one short of the need, and no record array at all."""
+    B = 5
+    pick = np.random.default_rng(S).random((B, S)) < 0.5
+    pick[:, 1] = pick[:, S - 1] = True                         # the first slot and the last one of the ragged trip
+    pick[:, 0] = False
+    where = {(b, i): ((6, 6) if pick[b, i] else (2, 6)) for b in range(B) for i in range(1, S) if pick[b, i] or i % 3 == 0}
+    stats = made_up_stats(B, S, where)
+    kw = dict(size=8, min_px=3, jitter_scale=0.5, jitter_shift=0.5, seed=11, scene_id_base=40)
+    want = R.select(oc.make_params(K, **kw), stats).view(np.int32).reshape(-1, 12)
+    need = len(want)
+    assert need == int(pick.sum()) and 0.35 * B * (S - 1) < need < 0.65 * B * (S - 1)
+    assert [tuple(r) for r in want[:, :2]] == [(b, i) for b in range(B) for i in range(1, S) if pick[b, i]]
+    st, n, got = select_only(stats, dev, **kw)
+    assert st == 0 and n == need and np.array_equal(got[:n], want) and (got[n:] == -1).all()
+    st, n, got = select_only(stats, dev, capacity=need - 1, **kw)
+    assert st == _abi.OBJECT_CROPS_CAPACITY and n == need       # the need, not what fitted
+    assert np.array_equal(got[:need - 1], want[:need - 1]) and (got[need - 1:] == -1).all()      # nothing at or behind the capacity
+    st, n, _ = select_only(stats, dev, capacity=0, null_records=True, **kw)
+    assert st == _abi.OBJECT_CROPS_CAPACITY and n == need
+
+
+def test_step_timer_needs_every_step(picture, dev):
+    """slhip_object_crops_timings (the step timer under the crops' convention): an error until both steps of the module were
+    timed since the last timing_enable(1); a refused call and a call with timing off record nothing."""
+    host, bufs = picture
+    L = _abi.lib()
+    ms = (C.c_float * 2)()
+
+    def read():
+        return L.slhip_object_crops_timings(C.byref(ms))
+
+    def extract():
+        return len(oc.extract(bufs, K, size=16, outputs=("instance",)))
+
+    try:
+        assert L.slhip_object_crops_timing_enable(1) == 0
+        assert select_only(host["stats"], dev, size=8)[0] == 0
+        assert read() == -1 and b"no timed calls" in L.slhip_last_error()      # a select alone
+        assert extract() > 0                                                    # select and gather
+        assert read() == 0 and all(np.isfinite(v) and v >= 0.0 for v in ms)
+        assert select_only(host["stats"], dev, size=0)[0] == -1                 # refused by its checks: the flags stay
+        assert read() == 0 and all(np.isfinite(v) and v >= 0.0 for v in ms)
+        assert L.slhip_object_crops_timing_enable(1) == 0                       # clears the flags
+        assert select_only(host["stats"], dev, size=0)[0] == -1
+        assert read() == -1 and b"no timed calls" in L.slhip_last_error()
+        assert L.slhip_object_crops_timing_enable(0) == 0
+        assert extract() > 0                                                    # timing off: nothing is recorded
+        assert read() == -1 and b"no timed calls" in L.slhip_last_error()
+    finally:
+        L.slhip_object_crops_timing_enable(0)
+
+
 # ---- 4. and 5. a real render ----------------------------------------------------------------------------------------------
 CROP_KW = dict(size=32, jitter_scale=0.25, jitter_shift=0.25, outputs=ALL)
 
@@ -299,7 +355,7 @@ def rendered(sl):
     host = dict(rgb=bufs.rgb.cpu().numpy(), coord=bufs.coord.cpu().numpy(), normals=bufs.normals.cpu().numpy(),
                 instance=bufs.instance.cpu().numpy()[..., 0].view(np.uint16),
                 whole=bufs.object_masks.dense("all", slots=range(7)).cpu().numpy(),
-                stats=oc._stats_records(bufs.object_stats).cpu().numpy().view(_abi.OBJECT_STATS_DTYPE).reshape(8, 7),
+                stats=bufs.object_stats.records().cpu().numpy().view(_abi.OBJECT_STATS_DTYPE).reshape(8, 7),
                 o2c=batch.object_to_camera.cpu().numpy().copy())
     return batch, bufs, crops, host
 

@@ -250,6 +250,33 @@ def test_project_refusals_leave_the_device_untouched(dev):
     assert b"" != _abi.lib().slhip_last_error()
 
 
+def test_step_timer_reads_an_untimed_step_as_minus_one(dev):
+    """slhip_object_keypoints_timings (the step timer under the keypoints' convention): -1.0 for a step that was not timed
+    since the last timing_enable(1); a call refused by its checks leaves the flags as they were."""
+    bank, ids, o2c = project_case()
+    L = _abi.lib()
+    ms = (C.c_float * 3)()
+
+    def read():
+        assert L.slhip_object_keypoints_timings(C.byref(ms)) == 0
+        return list(ms)
+
+    try:
+        assert L.slhip_object_keypoints_timing_enable(1) == 0
+        assert run_project(dev, bank, ids, o2c, Kp=33)[0] < 0
+        assert read() == [-1.0, -1.0, -1.0]
+        assert run_project(dev, bank, ids, o2c)[0] == 0                     # project alone
+        t = read()
+        assert t[0] == -1.0 and t[2] == -1.0 and np.isfinite(t[1]) and t[1] >= 0.0
+        assert run_project(dev, bank, ids, o2c, tol=-1.0)[0] < 0
+        t = read()
+        assert t[0] == -1.0 and t[2] == -1.0 and np.isfinite(t[1]) and t[1] >= 0.0
+        assert L.slhip_object_keypoints_timing_enable(1) == 0               # clears the flags
+        assert read() == [-1.0, -1.0, -1.0]
+    finally:
+        L.slhip_object_keypoints_timing_enable(0)
+
+
 # ---- 3. field --------------------------------------------------------------------------------------------------------------------
 FH, FW, FO = 19, 37, 3
 
@@ -417,9 +444,7 @@ def test_corners_meet_the_amodal_box(rendered):
     """(b) a corner keypoint inside the picture lies within one pixel of the object's amodal box whenever the picture does not
     clip that box; every scene has an object with all eight corners inside"""
     batch, table, bufs, bank, kps, pts = rendered
-    from stillleben_amd.object_crops import _stats_records
-
-    stats = _stats_records(bufs.object_stats).cpu().numpy().view(_abi.OBJECT_STATS_DTYPE).reshape(N_SCENES, N_OBJ + 1)
+    stats = bufs.object_stats.records().cpu().numpy().view(_abi.OBJECT_STATS_DTYPE).reshape(N_SCENES, N_OBJ + 1)
     uv, inside = kps.uv.cpu().numpy()[:, :, 9:], kps.inside.cpu().numpy()[:, :, 9:]
     checked = 0
     for s in range(N_SCENES):

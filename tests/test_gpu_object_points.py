@@ -375,7 +375,7 @@ def rendered(sl):
     S = N_OBJ + 1
     host = dict(rgb=bufs.rgb.cpu().numpy(), coord=bufs.coord.cpu().numpy(), normals=bufs.normals.cpu().numpy(),
                 instance=bufs.instance.cpu().numpy()[..., 0].view(np.uint16),
-                stats=op._stats_records(bufs.object_stats).cpu().numpy().view(_abi.OBJECT_STATS_DTYPE).reshape(N_SCENES, S),
+                stats=bufs.object_stats.records().cpu().numpy().view(_abi.OBJECT_STATS_DTYPE).reshape(N_SCENES, S),
                 mask_records=om.records.cpu().numpy().view(_abi.OBJECT_MASK_DTYPE).reshape(N_SCENES, S),
                 words=om.words.cpu().numpy().view(np.uint64), o2c=batch.object_to_camera.cpu().numpy().copy())
     return batch, bufs, pts, host

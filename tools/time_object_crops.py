@@ -11,7 +11,6 @@ and the same crops made by a torch composition on the same device: index_select 
 group, ObjectMasks.dense for the amodal masks.  The picture is made on the device from a seed: 20 rectangles per scene painted
 back to front, statistics and bit tiles to match (one tile box over the whole picture per slot).  Prints one JSON line.
     python tools/time_object_crops.py [scenes=512] [repeats=10] [size=128]"""
-import ctypes as C
 import json
 import os
 import statistics
@@ -24,8 +23,9 @@ import torch  # noqa: E402
 import torch.nn.functional as TF  # noqa: E402
 
 import stillleben_amd as sl  # noqa: E402
-from stillleben_amd import _abi  # noqa: E402
 from stillleben_amd import object_crops as oc  # noqa: E402
+
+import _step_timing  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 REP = max(3, int(sys.argv[2]) if len(sys.argv) > 2 else 10)
@@ -86,16 +86,7 @@ buffers.coord = torch.rand((B, H, W, 4), generator=g, device=dev)
 buffers.normals, buffers.instance = None, inst.view(B, H, W, 1)
 buffers.object_stats, buffers.object_masks = stats, masks
 
-L = _abi.lib()
-_abi.check(L.slhip_object_crops_timing_enable(1), "slhip_object_crops_timing_enable")
-times = []
-for r in range(2 + REP):                           # two warm-up calls: code objects, allocator
-    crops = oc.extract(buffers, K, **KW)
-    ms = (C.c_float * 2)()
-    _abi.check(L.slhip_object_crops_timings(C.byref(ms)), "slhip_object_crops_timings")
-    if r >= 2:
-        times.append((ms[0], ms[1]))
-_abi.check(L.slhip_object_crops_timing_enable(0), "slhip_object_crops_timing_enable")
+crops, times = _step_timing.timed("crops", 2, lambda: oc.extract(buffers, K, **KW), REP)
 n = len(crops)
 bx0, by0, side = (crops.box[:, k].double() for k in (0, 1, 2))
 area = ((bx0 + side).clamp(0, W) - bx0.clamp(0, W)) * ((by0 + side).clamp(0, H) - by0.clamp(0, H))      # the part inside the picture

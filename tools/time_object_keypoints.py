@@ -8,7 +8,6 @@ events of slhip_object_keypoints_timing_enable:
 and the torch formulation of the field a user would write today, in the same run on the same inputs: a gather of uv by
 instance, a subtract and a normalise.  The picture is made on the device from a seed.  Prints one JSON line.
     python tools/time_object_keypoints.py [scenes=64] [repeats=20] [slice=16]"""
-import ctypes as C
 import json
 import os
 import statistics
@@ -22,8 +21,10 @@ import torch  # noqa: E402
 
 import scenes as S  # noqa: E402
 import stillleben_amd as sl  # noqa: E402
-from stillleben_amd import _abi, synthetic  # noqa: E402
+from stillleben_amd import synthetic  # noqa: E402
 from stillleben_amd import object_keypoints as ok  # noqa: E402
+
+import _step_timing  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 REP = max(3, int(sys.argv[2]) if len(sys.argv) > 2 else 20)
@@ -33,18 +34,11 @@ K4 = (1066.778, 1067.487, 312.9869, 241.3109)
 HBM_COPY_TBPS = 6.29      # measured float4 copy on the MI355X, the roof of a streaming kernel
 sl.init_cuda(0)
 dev = torch.device("cuda", 0)
-L = _abi.lib()
-_abi.check(L.slhip_object_keypoints_timing_enable(1), "slhip_object_keypoints_timing_enable")
 
 
 def timed(fn, which, warm=2):
-    out, ms = None, []
-    for r in range(warm + REP):
-        out = fn()
-        t = (C.c_float * 3)()
-        _abi.check(L.slhip_object_keypoints_timings(C.byref(t)), "slhip_object_keypoints_timings")
-        if r >= warm:
-            ms.append(t[which])
+    out, times = _step_timing.timed("keypoints", 3, fn, REP, warm)
+    ms = [t[which] for t in times]
     return out, statistics.median(ms), ms
 
 
@@ -97,7 +91,6 @@ def field_call():
 
 
 _, field_ms, field_all = timed(field_call, 2, warm=len(firsts))
-_abi.check(L.slhip_object_keypoints_timing_enable(0), "slhip_object_keypoints_timing_enable")
 written = SLICE * H * W * Kp * 8
 read = SLICE * H * W * 2
 

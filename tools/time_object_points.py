@@ -8,7 +8,6 @@ same amount of work, other pixels; the tool therefore compares against it only w
 The picture is made on the device from a seed: 20 rectangles per scene painted back to front, statistics and bit tiles to match
 (one tile box over the whole picture per slot, the hardest case for the gather: 4800 words per set).  Prints one JSON line.
     python tools/time_object_points.py [scenes=512] [repeats=10] [points=1024]"""
-import ctypes as C
 import json
 import os
 import statistics
@@ -20,8 +19,9 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import stillleben_amd as sl  # noqa: E402
-from stillleben_amd import _abi  # noqa: E402
 from stillleben_amd import object_points as op  # noqa: E402
+
+import _step_timing  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 REP = max(3, int(sys.argv[2]) if len(sys.argv) > 2 else 10)
@@ -74,16 +74,7 @@ buffers.coord = torch.rand((B, H, W, 4), generator=g, device=dev) + 0.5
 buffers.rgb, buffers.normals, buffers.instance = None, None, inst.view(B, H, W, 1)
 buffers.object_stats, buffers.object_masks = stats, masks
 
-L = _abi.lib()
-_abi.check(L.slhip_object_points_timing_enable(1), "slhip_object_points_timing_enable")
-times = []
-for r in range(2 + REP):                           # two warm-up calls: code objects, allocator
-    points = op.extract(buffers, K4, **KW)
-    ms = (C.c_float * 2)()
-    _abi.check(L.slhip_object_points_timings(C.byref(ms)), "slhip_object_points_timings")
-    if r >= 2:
-        times.append((ms[0], ms[1]))
-_abi.check(L.slhip_object_points_timing_enable(0), "slhip_object_points_timing_enable")
+points, times = _step_timing.timed("points", 2, lambda: op.extract(buffers, K4, **KW), REP)
 n = len(points)
 # every point is a visible pixel of its object
 hit = inst[points.scene.long()[:, None], points.pixel[..., 1].long(), points.pixel[..., 0].long()] == points.slot[:, None]

@@ -7,7 +7,6 @@ events of slhip_object_regions_timing_enable:
 and the torch formulation a user would write today, in the same run on the same render: per class, gather the pixels of the
 class, a [P, R] plane of squared distances, argmin.  Prints one JSON line.
     python tools/time_object_regions.py [scenes=16] [repeats=20]"""
-import ctypes as C
 import json
 import os
 import statistics
@@ -23,23 +22,18 @@ import stillleben_amd as sl  # noqa: E402
 from stillleben_amd import _abi, synthetic  # noqa: E402
 from stillleben_amd import object_regions as og  # noqa: E402
 
+import _step_timing  # noqa: E402
+
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16
 REP = max(3, int(sys.argv[2]) if len(sys.argv) > 2 else 20)
 OBJ, RES, K4 = 20, (640, 480), (1066.778, 1067.487, 312.9869, 241.3109)      # bench.py's N_OBJECTS, RESOLUTION, INTRINSICS
 sl.init_cuda(0)
 dev = torch.device("cuda", 0)
-L = _abi.lib()
-_abi.check(L.slhip_object_regions_timing_enable(1), "slhip_object_regions_timing_enable")
 
 
 def timed(fn, which, warm=3):
-    out, ms = None, []
-    for r in range(warm + REP):
-        out = fn()
-        t = (C.c_float * 3)()
-        _abi.check(L.slhip_object_regions_timings(C.byref(t)), "slhip_object_regions_timings")
-        if r >= warm:
-            ms.append(t[which])
+    out, times = _step_timing.timed("regions", 3, fn, REP, warm)
+    ms = [t[which] for t in times]
     return out, statistics.median(ms), ms
 
 
@@ -107,5 +101,4 @@ for R in (64, 255):
     row["regions_seen_per_object"] = round(float((og.label(inst, coord, records, cen, n_objects=OBJ, histogram=True).histogram > 0)
                                                  .sum(dim=2).float().mean()), 2)
     result["R%d" % R] = row
-_abi.check(L.slhip_object_regions_timing_enable(0), "slhip_object_regions_timing_enable")
 print(json.dumps(result))

@@ -1370,6 +1370,7 @@ __device__ __forceinline__ float shadow_tap(const float* __restrict__ sm, int S,
 // shadow_tap() touch a 5x5 texel window; when the per-axis tap coordinates are consecutive (always,
 // except where rounding makes two taps share a texel) the window is fetched once and every tap is
 // evaluated from registers with exactly the arithmetic and summation order of the tap-by-tap form.
+template <bool kRef>
 __device__ __forceinline__ float shadow_pcf16(const float* __restrict__ sm, int S, float px, float py, float ref,
                                               const unsigned* __restrict__ tile_bits)
 {
@@ -1390,11 +1391,12 @@ __device__ __forceinline__ float shadow_pcf16(const float* __restrict__ sm, int 
     if (regular) {
         const float r = clampf(ref, 0.0f, 1.0f);
         unsigned off_y[5];
-        int cx[5];
+        int cx[5], cy[5];
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
             cx[k] = min(max(ix[0] + k, 0), S - 1);
-            off_y[k] = (unsigned)min(max(iy[0] + k, 0), S - 1) * (unsigned)S;
+            cy[k] = min(max(iy[0] + k, 0), S - 1);
+            off_y[k] = (unsigned)cy[k] * (unsigned)S;
         }
         if (tile_bits) {
             // The shadow raster files which 64 x 64-texel tiles of the map its casters touched (the bits k_shadow_restore clears the
@@ -1402,7 +1404,9 @@ __device__ __forceinline__ float shadow_pcf16(const float* __restrict__ sm, int 
             // (r <= 1), every tap is exactly 1 -- the same 1.0 as below, without fetching the window.  Most of the background plane.
             const int tn = shadow_tiles_x(S);
             const int ta = cx[0] / kShadowTile, tb = cx[4] / kShadowTile;
-            const int ra = (int)(off_y[0] / (unsigned)S) / kShadowTile, rb = (int)(off_y[4] / (unsigned)S) / kShadowTile;
+            // (the clamped rows themselves: dividing off_y by S to get them back is two per-lane 32-bit divisions per lit pixel)
+            const int ra = (kRef ? (int)(off_y[0] / (unsigned)S) : cy[0]) / kShadowTile;
+            const int rb = (kRef ? (int)(off_y[4] / (unsigned)S) : cy[4]) / kShadowTile;
             const int t00 = ra * tn + ta, t01 = ra * tn + tb, t10 = rb * tn + ta, t11 = rb * tn + tb;
             const unsigned touched = ((tile_bits[t00 >> 5] >> (t00 & 31)) | (tile_bits[t01 >> 5] >> (t01 & 31)) |
                                       (tile_bits[t10 >> 5] >> (t10 & 31)) | (tile_bits[t11 >> 5] >> (t11 & 31))) & 1u;
@@ -1451,6 +1455,7 @@ __device__ __forceinline__ float shadow_pcf16(const float* __restrict__ sm, int 
 // per channel in the kernel that is bound by VALU issue.  0 -> exp2(-inf) = 0.
 __device__ __forceinline__ float pow22(float x) { return __builtin_amdgcn_exp2f(2.2f * __builtin_amdgcn_logf(x)); }
 
+template <bool kRef>
 __device__ __forceinline__ void shade_fragment(const slhip_scene* __restrict__ sc, const slhip_draw* __restrict__ dr,
                                                const float* base, const float* world, const float* nrm_in,
                                                bool front_facing, const float* __restrict__ shadow, int S, int shadow_lights,
@@ -1493,7 +1498,7 @@ __device__ __forceinline__ void shade_fragment(const slhip_scene* __restrict__ s
             const float py = fmaf(pc[1] * rpw, 0.5f, 0.5f);
             const float pz = fmaf(pc[2] * rpw, 0.5f, 0.5f);
             const float* sm = shadow + (size_t)i * S * S;
-            inverse_shadow = shadow_pcf16(sm, S, px, py, (pz - 0.00003f), shadow_tiles ? shadow_tiles + (size_t)i * shadow_tile_words(S) : nullptr);
+            inverse_shadow = shadow_pcf16<kRef>(sm, S, px, py, (pz - 0.00003f), shadow_tiles ? shadow_tiles + (size_t)i * shadow_tile_words(S) : nullptr);
         }
         float L[3] = {-ld[0], -ld[1], -ld[2]};
         normalize3_fast(L);
@@ -1650,6 +1655,11 @@ struct ShadeParams {
 };
 
 // The corners' vertex-stage outputs and window coordinates come from the records k_vertex_xform wrote (`vattr`).
+// kRef (SLHIP_SHADE_REFERENCE=1 at run time): the in-library reference of two pieces the default form does in fewer instructions
+// and with the same bits -- the block's exposure sum behind one barrier and the PCF tile rows without a division (shadow_pcf16);
+// tests/test_gpu_shade_paths.py holds the two forms against each other.  The default form fits 128 VGPRs, four waves per SIMD,
+// without an occupancy attribute; the reference form takes 130 and runs three (profiles/r11).
+template <bool kRef>
 __global__ __launch_bounds__(256) SLHIP_SHADE_KERNEL void k_shade(slhip_mesh_pool pool, const slhip_scene* __restrict__ scenes,
                                                const slhip_draw* __restrict__ draws, ShadeParams prm,
                                                const unsigned long long* __restrict__ vis,
@@ -1671,6 +1681,9 @@ __global__ __launch_bounds__(256) SLHIP_SHADE_KERNEL void k_shade(slhip_mesh_poo
     // one 128-byte line.  Otherwise: 256 consecutive pixels per block.  Placement only: the values do not depend on it.
     unsigned pix;
     bool active;
+    // (The pixel's column and row are divided out of `pix` where they are used.  Carried in two registers from here they cost the
+    // kernel its fourth wave per SIMD -- 129 VGPRs, 16.9 instead of 14.8 ms -- and formed again from the thread index at each use
+    // they were 0.15 ms slower than the divisions: profiles/r11.)
     if (prm.tiled) {
         const unsigned per_row = (unsigned)W >> 5, l = threadIdx.x & 63u;
         const unsigned tx = (blk % per_row) * 32u + (threadIdx.x >> 6) * 8u + (l & 7u), ty = (blk / per_row) * 8u + (l >> 3);
@@ -1868,7 +1881,7 @@ __global__ __launch_bounds__(256) SLHIP_SHADE_KERNEL void k_shade(slhip_mesh_poo
                 const float* sm = (prm.flags & SLHIP_RENDER_SHADOWS) && shadow
                                       ? shadow + (size_t)scene * prm.shadow_lights * prm.S * prm.S
                                       : nullptr;
-                shade_fragment(sc, dr, base, world, nrm, front, sm, prm.S, prm.shadow_lights,
+                shade_fragment<kRef>(sc, dr, base, world, nrm, front, sm, prm.S, prm.shadow_lights,
                                sm && shadow_tiles ? shadow_tiles + (size_t)scene * SLHIP_NUM_LIGHTS * shadow_tile_words(prm.S) : nullptr, lm, roughness, metallic, occlusion, emissive, color, nout);
                 cls = dr->class_index & 0xFFFFu;
                 inst = dr->instance_index & 0xFFFFu;
@@ -1954,6 +1967,26 @@ __global__ __launch_bounds__(256) SLHIP_SHADE_KERNEL void k_shade(slhip_mesh_poo
 #pragma unroll
         for (int c = 0; c < 4; ++c) red[c][threadIdx.x] = lum_color[c];
         __syncthreads();
+        if (!kRef) {
+            // The tree below, with ONE barrier.  Its strides 128 and 64 leave t[i] = (x0[i] + x2[i]) + (x1[i] + x3[i]) over the four
+            // waves' lane values in lane i < 64; its strides 32 .. 1 stay inside wave 0: lane i < s takes own + lane i + s, and what
+            // the lanes >= s hold afterwards is never read, as below.  The same pairing, hence the same bits; three waves leave at once.
+            if (threadIdx.x < 64) {
+                float t[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    t[c] = (red[c][threadIdx.x] + red[c][threadIdx.x + 128]) + (red[c][threadIdx.x + 64] + red[c][threadIdx.x + 192]);
+#pragma unroll
+                for (int s = 32; s > 0; s >>= 1)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) t[c] += __shfl_down(t[c], s, 64);
+                if (threadIdx.x == 0) {
+                    float* part = lum_part + ((size_t)scene * blocks_per_scene + blk) * 4;
+                    part[0] = t[0]; part[1] = t[1]; part[2] = t[2]; part[3] = t[3];
+                }
+            }
+            return;
+        }
         for (int s = 128; s > 0; s >>= 1) {
             if (threadIdx.x < s) {
 #pragma unroll
@@ -2803,11 +2836,17 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
     const bool ssao_tiled = ssao && want_rgb && ssao_tiled_on && prm.tiled && H % 16 == 0 && W % 32 == 0 && (W / 8 + 1) * (H / 8 + 1) * 4 <= 60000;
     float2* ssao_tiles = ssao_tiled ? reinterpret_cast<float2*>(reinterpret_cast<char*>(scratch->d_ao) + ssao_tiles_offset(n_scenes, W, H)) : nullptr;
     unsigned char* ssao_skip = ssao_tiled ? reinterpret_cast<unsigned char*>(ssao_tiles + (size_t)n_scenes * ssao_tiles_per_scene(W, H)) : nullptr;
-    k_shade<<<pix_blocks, 256, 0, stream>>>(*pool, d_scenes, d_draws, prm,
-                                            reinterpret_cast<const unsigned long long*>(scratch->d_vis), *out, hdr0,
-                                            shadows ? scratch->d_shadow : nullptr, scratch->d_lum, clipbuf,
-                                            ssao ? scratch->d_ao + (size_t)n_scenes * P : nullptr, vattr, ssao_tiles,
-                                            shadows && !getenv("SLHIP_NO_PCF_TILES") ? scratch->d_shadow_tiles : nullptr);
+    // developer knob, read at every call like SLHIP_RASTER_WIDE: 1 = k_shade<true>, the in-library reference of the default form
+    const int shade_reference = getenv("SLHIP_SHADE_REFERENCE") ? atoi(getenv("SLHIP_SHADE_REFERENCE")) : 0;
+    auto launch_shade = [&](auto kernel) {
+        kernel<<<pix_blocks, 256, 0, stream>>>(*pool, d_scenes, d_draws, prm,
+                                               reinterpret_cast<const unsigned long long*>(scratch->d_vis), *out, hdr0,
+                                               shadows ? scratch->d_shadow : nullptr, scratch->d_lum, clipbuf,
+                                               ssao ? scratch->d_ao + (size_t)n_scenes * P : nullptr, vattr, ssao_tiles,
+                                               shadows && !getenv("SLHIP_NO_PCF_TILES") ? scratch->d_shadow_tiles : nullptr);
+    };
+    if (shade_reference) launch_shade(k_shade<true>);
+    else launch_shade(k_shade<false>);
     SLHIP_LAUNCH_CHECK();
     if (shadows && n_chunks > 0) {   // the maps were read for the last time: marked tiles back to 1.0
         k_shadow_restore<<<n_tile_words, 256, 0, stream>>>(reinterpret_cast<unsigned*>(scratch->d_shadow), scratch->d_shadow_tiles,

@@ -633,7 +633,12 @@ int slhip_diff_pose_backward_batch(const uint8_t* d_rgb, const float* d_coord, c
 int slhip_light_map_floats(uint32_t env_size, uint32_t env_levels, uint32_t irr_size, uint32_t pre_size,
                            uint32_t pre_levels, uint32_t lut_size, uint64_t out[4]);
 /* d_equirect: f32 [H][W][3] equirectangular radiance, row 0 = top (+z up, azimuth atan2(y, x) along
- * the row); fills every buffer of *lm (a HOST struct holding DEVICE pointers).                   */
+ * the row); fills every buffer of *lm (a HOST struct holding DEVICE pointers).  The image is read
+ * bilinearly at u = atan2(y, x) * 0.1591 + 0.5, w = asin(z) * 0.3183 + 0.5 (w = 1: top row) and clamped
+ * to its edge in both directions, as the reference's ClampToEdge sampler: not wrapped at azimuth +-pi.
+ * The irradiance pass keeps the reference's tangent frame right = (0, 1, 0) x N, up = N x right WITHOUT
+ * normalising either (cubemap_shader_irradiance.frag:22-24).  tests/ibl_analytic.py restates these rules
+ * in float64.                                                                                      */
 int slhip_light_map_build(const float* d_equirect, int H, int W, const slhip_light_map* lm, void* stream);
 
 /* ---------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """Image-based lighting ('next' row f1) on the GPU: the precompute kernels against the oracle
 (oracle/ibl_ref.c, same sampling rules and operation order; libm vs device transcendentals differ in
-the last bits, so float tolerances apply), the `.ibl` / Radiance-HDR loaders, and the lights an sIBL
-file names."""
+the last bits, so float tolerances apply) and against the float64 known answers of tests/ibl_analytic.py
+(no oracle involved: maps, sky and IBL shading of a radiance linear in the direction), the `.ibl` /
+Radiance-HDR loaders, and the lights an sIBL file names."""
 import math
 import os
 
@@ -63,12 +64,13 @@ def test_precompute_matches_oracle(sl, oracle):
 
 
 def test_physical_sanity_of_the_maps(sl):
-    """A constant white environment: irradiance = pi * L (cosine-weighted hemisphere), every prefilter level
-    = L, and the BRDF table's scale + bias stays in (0, 1]."""
+    """A constant white environment: irradiance = 0.9941 L (the reference normalises its cosine-weighted sum by
+    pi / nrSamples, so the constant comes back, not pi times it), every prefilter level = L, and the BRDF
+    table's scale + bias stays in (0, 1]."""
     eq = np.ones((16, 32, 3), np.float32)
     lm = sl.LightMap(eq, sizes=SMALL)
     irr = lm.irradiance.cpu().numpy().reshape(-1, 4)[:, :3]
-    # the reference's Riemann sum (delta = 0.02) of cos * sin over the hemisphere, times pi / nrSamples
+    # the reference's Riemann sum (delta = 0.02): pi / nrSamples * sum(cos sin) over 315 x 79 steps = pi / 79 * 24.9995 = 0.9941
     assert np.abs(irr - irr.mean()).max() < 1e-4 and abs(irr.mean() - 1.0) < 0.02
     pre = lm.prefilter.cpu().numpy().reshape(-1, 4)[:, :3]
     assert np.abs(pre - 1.0).max() < 1e-4
@@ -238,3 +240,127 @@ def test_background_image_and_exposure_average(sl, oracle):
     assert top[:, 0].mean() > bottom[:, 0].mean() + 20         # upright: the red half of the image is at the top
     covered = ~empty[0]
     assert np.array_equal(rgb[0][covered][:, :3], rgb[1][covered][:, :3])   # objects: identical exposure with / without background
+
+
+# ---- float64 known answers (tests/ibl_analytic.py): no oracle involved ------------------------------------------------------------
+# Tolerance = the CPU bound of ibl_analytic.BOUNDS (oracle vs float64, measured in tests/test_oracle_ibl.py) plus the margin this
+# file grants the device's sinf / cosf / atan2f / asinf / log2f / powf against libm in test_precompute_matches_oracle above:
+# |gpu - float64| <= |oracle - float64| + |gpu - oracle|.  (rtol, atol) per map; the HDR image's is test_gpu_render's 1e-3 relative.
+GPU_MARGIN = {"env": (1e-4, 1e-4), "irradiance": (2e-3, 1e-4), "prefilter": (5e-3, 1e-3), "brdf_lut": (1e-4, 1e-5)}
+HDR_RTOL = 1e-3
+
+
+@pytest.fixture(scope="module")
+def analytic_maps(sl):
+    """sl.LightMap of both linear radiances at the full and the coarse sizes: built once."""
+    import ibl_analytic as A
+    from test_oracle_ibl import equirect_f32
+
+    return {(p, which): sl.LightMap(equirect_f32(p), sizes=sizes)
+            for p in range(len(A.PAIRS)) for which, sizes in (("full", A.SIZES), ("coarse", A.SIZES_COARSE))}
+
+
+def over_tolerance(got, want, bound, margin):
+    rtol, atol = margin
+    err = np.abs(got - want)
+    print("max error %.3g (bound %s + %g relative + %g)" % (err.max(), np.max(bound), rtol, atol))
+    return err > bound + rtol * np.abs(want) + atol
+
+
+@pytest.mark.parametrize("pair", [0, 1])
+def test_precompute_matches_float64_reference(analytic_maps, pair):
+    import ibl_analytic as A
+    from test_oracle_ibl import env_texel_classes
+
+    lm, sz = analytic_maps[pair, "full"], A.SIZES
+    env = A.cube_levels(lm.env.cpu().numpy(), sz["env_size"], sz["env_levels"])[0]
+    pole, seam, inner = env_texel_classes(sz["env_size"], *A.EQUIRECT_SHAPE)
+    bound = np.where(pole, A.BOUNDS["env_all"], np.where(seam, A.BOUNDS["env_seam"], A.BOUNDS["env_inner"]))[..., None]
+    assert not over_tolerance(env[..., :3], A.env0(pair, sz["env_size"]), bound, GPU_MARGIN["env"]).any()
+    assert (env[..., 3] == 1.0).all()
+    irr = A.cube_levels(lm.irradiance.cpu().numpy(), sz["irr_size"], 1)[0]
+    assert not over_tolerance(irr[..., :3], A.irradiance(pair, sz["irr_size"]), A.BOUNDS["irradiance"], GPU_MARGIN["irradiance"]).any()
+    over = []
+    for l, pre in enumerate(A.cube_levels(lm.prefilter.cpu().numpy(), sz["pre_size"], sz["pre_levels"])):
+        want = A.prefilter(pair, sz["pre_size"] >> l, A.level_roughness(l, sz["pre_levels"]))
+        over.append(over_tolerance(pre[..., :3], want, A.BOUNDS["prefilter_%d" % l], GPU_MARGIN["prefilter"]).ravel())
+    assert np.concatenate(over).mean() <= 1e-3           # isolated texels only, as test_precompute_matches_oracle allows
+    lut = lm.brdf_lut.cpu().numpy().reshape(sz["lut_size"], sz["lut_size"], 2)
+    assert not over_tolerance(lut, A.brdf_lut(sz["lut_size"]), A.BOUNDS["brdf_lut"], GPU_MARGIN["brdf_lut"]).any()
+
+
+def test_mip_chain_of_the_large_map_is_the_exact_box_filter(analytic_maps):
+    from test_oracle_ibl import check_mip_chain
+
+    assert check_mip_chain(analytic_maps[0, "full"].env.cpu().numpy(), 512, 10)[-1].shape[1] == 1
+
+
+@pytest.mark.parametrize("shape,value", [((1, 1), (1.0, 1.0, 1.0)), ((1, 2), (0.25, 2.0, 7.5)), ((2, 1), (1.0, 0.5, 3.0)),
+                                         ((3, 5), (0.25, 2.0, 7.5))])
+def test_tiny_and_constant_images(sl, shape, value):
+    """Images of 1 x 1, 1 x 2, 2 x 1 (and an odd one): every bilinear read clamps.  A constant image gives the constant."""
+    import ibl_analytic as A
+    from test_oracle_ibl import check_constant_maps
+
+    eq = np.broadcast_to(np.asarray(value, np.float32), shape + (3,)).copy()
+    lm = sl.LightMap(eq, sizes=A.SIZES_COARSE)
+    bufs = {k: getattr(lm, k).cpu().numpy() for k in ("env", "irradiance", "prefilter", "brdf_lut")}
+    check_constant_maps(bufs, value, A.SIZES_COARSE)
+    rng = np.random.default_rng(shape[0] * 2 + shape[1])
+    lm = sl.LightMap((0.2 + rng.random(shape + (3,))).astype(np.float32), sizes=A.SIZES_COARSE)
+    for k in ("env", "irradiance", "prefilter", "brdf_lut"):
+        assert torch.isfinite(getattr(lm, k)).all(), k
+
+
+def max_radiance(pair):
+    import ibl_analytic as A
+
+    a, B = A.PAIRS[pair]
+    return float((a + np.linalg.norm(B, axis=1)).max())
+
+
+def render_hdr(scene_list):
+    from stillleben_amd import _abi
+    from stillleben_amd._context import engine
+
+    W, H = scene_list[0].viewport
+    B = len(scene_list)
+    bufs = engine().render(scene_list, _abi.OUT_ALL, ssao=False, shadows=False, keep_hdr=True)
+    torch.cuda.synchronize()
+    hdr = bufs._keepalive[0]["hdr"].view(torch.float32)[: B * H * W * 4].reshape(B, H, W, 4).cpu().numpy()
+    return bufs, hdr
+
+
+@pytest.mark.parametrize("which", ["full", "coarse"])
+@pytest.mark.parametrize("pair", [0, 1])
+def test_sky_is_the_radiance_along_the_pixel_ray(sl, analytic_maps, pair, which):
+    """The sky of tests/test_oracle_ibl.py on the kernels' float image: every empty pixel holds L(its world direction), the
+    direction taken from the camera coordinates of a sheet that fills the same view."""
+    from test_oracle_ibl import assert_within, report, sky_directions, sky_errors, sky_scenes
+
+    lm = analytic_maps[pair, which]
+    covered, empty = sky_scenes(sl, lm)
+    bufs, hdr = render_hdr([covered, empty])
+    inst = bufs.instance.cpu().numpy()
+    dirs = sky_directions(covered, bufs.cam_coord.cpu().numpy()[0], inst[0])
+    assert (inst[1] == 0).all()
+    fig = sky_errors(hdr[1], dirs, pair, lm.sizes["env_size"])
+    report("pair %d sky" % pair, fig)
+    # the sky is a bilinear (convex) read of the environment's texels: the environment's own margin carries over
+    assert_within(fig, extra=lambda k: GPU_MARGIN["env"][1] + GPU_MARGIN["env"][0] * max_radiance(pair))
+
+
+@pytest.mark.parametrize("pair", [0, 1])
+def test_ibl_shading_known_answer(sl, analytic_maps, pair):
+    """The IBL term of k_shade at the centre of a tilted face, lit by the light map only, against the float64 split sum."""
+    from test_oracle_ibl import assert_within, report, shading_errors, shading_scenes
+
+    scs = shading_scenes(sl, analytic_maps[pair, "full"])
+    bufs, hdr = render_hdr(scs)
+    fig = shading_errors(scs, hdr, bufs.cam_coord.cpu().numpy(), bufs.instance.cpu().numpy(), pair)
+    report("pair %d shading" % pair, fig)
+    # the term is FssEss * prefilter + (FmsEms + k_D) * irradiance with weights that sum to less than one: the looser of the two
+    # maps' margins carries over, plus test_gpu_render's 1e-3 relative for k_shade's own arithmetic; values stay below max L
+    rtol, atol = GPU_MARGIN["prefilter"]
+    assert_within({k: v for k, v in fig.items() if not k.endswith("_signal")},
+                  extra=lambda k: atol + (rtol + HDR_RTOL) * max_radiance(pair))

@@ -51,7 +51,9 @@ extern "C" {
                                     slhip_object_keypoints_check_params, _fps_bytes, _fps, _fps_host, _project, _field,
                                     _timing_enable, _timings;
                                     slhip_object_regions_check_params, _centres_bytes, _centres, _centres_host, _vertices,
-                                    _vertices_host, _label, _label_host, _timing_enable, _timings */
+                                    _vertices_host, _label, _label_host, _timing_enable, _timings;
+                                    slhip_pose_error_check_params, _diameter, _diameter_host, slhip_pose_error,
+                                    slhip_pose_error_host, _timing_enable, _timings */
 #define SLHIP_NUM_LIGHTS 3 /* reference include/stillleben/common.h:17 */
 
 /* ---------------------------------------------------------------------------------------------
@@ -1061,6 +1063,100 @@ int slhip_object_regions_label_host(const slhip_object_region_params* params, co
  * work; slhip_object_regions_timings waits for them and gives the ms of the last centres, vertices and label (-1: not run). */
 int slhip_object_regions_timing_enable(int on);
 int slhip_object_regions_timings(float ms_out[3]);
+
+/* ---------------------------------------------------------------------------------------------
+ * Pose errors: ADD, ADD-S (PoseCNN, DenseFusion), BOP's MSSD and MSPD of pose estimates against a
+ * batch's ground truth object_to_camera, with the symmetries of every class; the arg-min of MSSD is
+ * the symmetric equivalent of the ground truth nearest the estimate, the target of symmetry-aware
+ * losses.  This project's addition, the reference has no counterpart.  All float32, one rounded IEEE
+ * operation at a time (no fma); csrc/slhip_pose_rules.h holds the rules for host and device,
+ * tests/pose_error_ref.py restates them in NumPy bit for bit.  DESIGN.md "Pose errors".
+ *
+ * The bank: per class a (0 <= a < n_assets) count[a] points (x, y, z, 1) in the object frame -- row a of
+ * points, n_points floats4 long -- and n_sym[a] symmetry transforms, 3 x 4 row-major, entry 0 the identity
+ * -- row a of symmetries, n_symmetries long.  A class with count outside [1, n_points] or n_sym outside
+ * [1, n_symmetries], and a class index outside the bank, has no points: its errors are +inf and its
+ * indices -1 (never 0, which would read as a perfect pose).  The points must be finite.
+ *
+ * Per (scene, object, hypothesis) with g = the object's ground truth and e the estimate (3 x 4 row-major):
+ *   D = e - g, all twelve entries (the translations cancel before anything is multiplied).  When an entry of D
+ * is not finite, every error of the hypothesis is NaN and every index -1.  Otherwise, with M p = the rows
+ * ((m0*x + m1*y) + m2*z) + m3, dist2(a, b) = ((ax-bx)^2 + (ay-by)^2) + (az-bz)^2 and p_i the class's points:
+ *   w_i = D p_i                      the camera-frame displacement x_e(p_i) - x_g(p_i)
+ *   v_i[c] = (g[0][c]*w_i[0] + g[1][c]*w_i[1]) + g[2][c]*w_i[2]      R_g^T w_i (the rotation of g is taken as orthonormal)
+ *   q_i = p_i + v_i per component    the estimate's point in the ground truth's object frame
+ *   add   = sum_i sqrt((w_i[0]^2 + w_i[1]^2) + w_i[2]^2) / (float)count
+ *   adds  = sum_i sqrt(min_j dist2(q_i, p_j)) / (float)count
+ *   mssd  = sqrt(min_s max_i dist2(q_i, S_s p_i)),  mssd_sym = the lowest s that reaches the minimum
+ *   mspd  = sqrt(min_s max_i ((ue_i - ug_si)^2 + (ve_i - vg_si)^2)),  mspd_sym likewise, where
+ *           (X, Y, Z) = e p_i,  ue = (fx * X) / Z + cx,  ve = (fy * Y) / Z + cy,  and ug, vg the same of g (S_s p_i);
+ *           when a Z of either side (any i, any s < n_sym) is not > 0:  mspd = +inf, mspd_sym = -1
+ * sqrt and / correctly rounded; min and max are order-free.  The order of the two sums: lane l of 256
+ * adds the terms of points l, l + 256, ... upwards from 0.0f; the 64 lanes of a wave combine by
+ * v[l] = v[l] + v[l ^ off] for off = 32, 16, 8, 4, 2, 1, the four waves as ((w0 + w1) + w2) + w3.
+ * An estimate equal to the ground truth has D = 0 and q_i = p_i to the bit: every error is exactly 0.
+ * The diameter of a class is sqrt(max_ij dist2(p_i, p_j)), 0 for a class without points.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_POSE_POINTS_MAX     4096
+#define SLHIP_POSE_SYMMETRIES_MAX 1024
+#define SLHIP_POSE_OUT_ADD  1u
+#define SLHIP_POSE_OUT_ADDS 2u
+#define SLHIP_POSE_OUT_MSSD 4u      /* mssd and mssd_sym */
+#define SLHIP_POSE_OUT_MSPD 8u      /* mspd and mspd_sym */
+
+typedef struct {
+    float fx, fy, cx, cy;      /* intrinsics of MSPD; fx, fy > 0, all finite                                  */
+    uint32_t n_objects;        /* O, objects per scene, 1..SLHIP_SYNTH_MAX_OBJECTS                            */
+    uint32_t n_hypotheses;     /* Hy >= 1, estimates per object                                               */
+    uint32_t outputs;          /* SLHIP_POSE_OUT_* bits, at least one                                         */
+    uint32_t _pad;
+} slhip_pose_error_params; /* 32 bytes */
+
+typedef struct {
+    const float* points;       /* f32 [n_assets, n_points, 4], 16-byte aligned                                */
+    const int32_t* count;      /* i32 [n_assets]                                                              */
+    const float* symmetries;   /* f32 [n_assets, n_symmetries, 3, 4], 16-byte aligned                         */
+    const int32_t* n_sym;      /* i32 [n_assets]                                                              */
+    uint32_t n_assets;         /* 1..SLHIP_SYNTH_MAX_ASSETS                                                   */
+    uint32_t n_points;         /* N, the row length: 1..SLHIP_POSE_POINTS_MAX                                 */
+    uint32_t n_symmetries;     /* S, the row length: 1..SLHIP_POSE_SYMMETRIES_MAX                             */
+    uint32_t _pad;
+} slhip_pose_bank; /* 48 bytes; the four arrays on the device, or on the host for the _host entries */
+
+typedef struct {               /* each [n_scenes, n_objects, n_hypotheses]; read only when its bit is set    */
+    float* add;
+    float* adds;
+    float* mssd;
+    int32_t* mssd_sym;
+    float* mspd;
+    int32_t* mspd_sym;
+} slhip_pose_error_out;
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_pose_error_check_params(const slhip_pose_error_params* params);
+/* d_diameter f32 [n_assets]: the entry zeroes it on `stream`, then all pairs of every class's points.  Runs once per table.
+ * A null pointer, a misaligned bank and row lengths out of range are refused before anything touches the device.
+ * Asynchronous on `stream`.                                                                                              */
+int slhip_pose_error_diameter(const slhip_pose_bank* bank, float* d_diameter, void* stream);
+/* The same rule on host arrays.  Host only, no device. */
+int slhip_pose_error_diameter_host(const slhip_pose_bank* h_bank, float* h_diameter);
+/* d_classes i32, read at (scene * O + object) * class_stride (1: a plain [n_scenes, O] tensor, 4: the asset of
+ * slhip_synth_object records in place); d_gt f32 [n_scenes, O, 3, 4] (object_to_camera of slhip_synth_place_view); d_est f32
+ * [n_scenes, O, Hy, 3, 4].  Every output named in params->outputs is written exactly once per hypothesis, the others are not
+ * touched.  n_scenes == 0 does nothing; null pointers (an output named in the mask included), a misaligned bank, row lengths
+ * out of range, class_stride 0, Hy == 0 and bad parameters are refused before anything touches the device.  One workgroup
+ * holds a class's points in LDS and takes one or several hypotheses of an object.  Asynchronous on `stream`.             */
+int slhip_pose_error(const slhip_pose_error_params* params, const slhip_pose_bank* bank, const int32_t* d_classes,
+                     uint32_t class_stride, const float* d_gt, const float* d_est, uint32_t n_scenes,
+                     const slhip_pose_error_out* out, void* stream);
+/* The same rules on host arrays through csrc/slhip_pose_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_pose_error_host(const slhip_pose_error_params* params, const slhip_pose_bank* h_bank, const int32_t* h_classes,
+                          uint32_t class_stride, const float* h_gt, const float* h_est, uint32_t n_scenes,
+                          const slhip_pose_error_out* out);
+/* Developer hook (tools/time_pose_error.py): with timing on, the two device calls record HIP events around their work;
+ * slhip_pose_error_timings waits for them and gives the ms of the last diameter and the last errors (-1: not run).       */
+int slhip_pose_error_timing_enable(int on);
+int slhip_pose_error_timings(float ms_out[2]);
 
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle

@@ -34,6 +34,8 @@ from . import object_keypoints  # noqa: F401  (additive: FPS keypoint banks, the
 from .object_keypoints import KeypointBank, ObjectKeypoints  # noqa: F401
 from . import object_regions  # noqa: F401  (additive: surface-region banks, per-vertex and per-pixel region labels)
 from .object_regions import RegionBank, ObjectRegions  # noqa: F401
+from . import pose_error  # noqa: F401  (additive: ADD, ADD-S, MSSD, MSPD against a batch's ground truth, with class symmetries)
+from .pose_error import ModelBank, PoseErrors  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -42,6 +44,7 @@ __all__ = [
     'camera_model', 'diff', 'extension', 'losses', 'quat_to_matrix', 'matrix_to_quat', 'ObjectStats', 'ObjectMasks', 'EnvironmentBank',
     'bop', 'depth_sensor', 'object_crops', 'ObjectCrops', 'object_points', 'ObjectPoints',
     'object_keypoints', 'KeypointBank', 'ObjectKeypoints', 'object_regions', 'RegionBank', 'ObjectRegions',
+    'pose_error', 'ModelBank', 'PoseErrors',
 ]
 
 

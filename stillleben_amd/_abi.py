@@ -50,6 +50,8 @@ OBJECT_POINTS_MAX = 16384
 KEYPOINTS_MAX = 32            # SLHIP_KEYPOINTS_MAX
 KEYPOINT_IN_FRONT, KEYPOINT_INSIDE, KEYPOINT_UNOCCLUDED = 1, 2, 4      # SLHIP_KEYPOINT_*: the flag bits of a projected keypoint
 KEYPOINT_FIELD_OFFSET, KEYPOINT_FIELD_UNIT = 0, 1                      # SLHIP_KEYPOINT_FIELD_*
+POSE_POINTS_MAX, POSE_SYMMETRIES_MAX = 4096, 1024                      # SLHIP_POSE_POINTS_MAX, SLHIP_POSE_SYMMETRIES_MAX
+POSE_OUT_ADD, POSE_OUT_ADDS, POSE_OUT_MSSD, POSE_OUT_MSPD = 1, 2, 4, 8      # SLHIP_POSE_OUT_*
 REGIONS_MAX, REGION_NONE = 255, 255                                    # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
 REGIONS_OUT_LOCAL, REGIONS_OUT_HISTOGRAM = 1, 2                        # SLHIP_REGIONS_OUT_*
 ABI_VERSION = 5
@@ -279,6 +281,29 @@ OBJECT_REGION_PARAMS_DTYPE = np.dtype([
     ("n_assets", np.uint32), ("outputs", np.uint32), ("_pad", np.uint32),
 ])
 assert OBJECT_REGION_PARAMS_DTYPE.itemsize == 32
+# slhip_pose_error_params (include/slhip.h), 32 bytes
+POSE_ERROR_PARAMS_DTYPE = np.dtype([
+    ("fx", np.float32), ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("n_objects", np.uint32),
+    ("n_hypotheses", np.uint32), ("outputs", np.uint32), ("_pad", np.uint32),
+])
+assert POSE_ERROR_PARAMS_DTYPE.itemsize == 32
+
+
+class PoseBank(C.Structure):
+    """slhip_pose_bank: the arrays of a model bank (device pointers, or host pointers for the _host entries)."""
+
+    _fields_ = [("points", C.c_void_p), ("count", C.c_void_p), ("symmetries", C.c_void_p), ("n_sym", C.c_void_p),
+                ("n_assets", C.c_uint32), ("n_points", C.c_uint32), ("n_symmetries", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+assert C.sizeof(PoseBank) == 48
+
+
+class PoseErrorOut(C.Structure):
+    """slhip_pose_error_out: the output pointers of slhip_pose_error."""
+
+    _fields_ = [("add", C.c_void_p), ("adds", C.c_void_p), ("mssd", C.c_void_p), ("mssd_sym", C.c_void_p), ("mspd", C.c_void_p),
+                ("mspd_sym", C.c_void_p)]
 
 
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
@@ -495,6 +520,16 @@ def lib():
                                                       C.c_void_p, C.c_void_p, C.c_void_p]
         L.slhip_object_regions_timing_enable.argtypes = [C.c_int]
         L.slhip_object_regions_timings.argtypes = [C.POINTER(C.c_float * 3)]
+    if hasattr(L, "slhip_pose_error"):               # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_pose_error_check_params.argtypes = [C.c_void_p]
+        L.slhip_pose_error_diameter.argtypes = [C.POINTER(PoseBank), C.c_void_p, C.c_void_p]
+        L.slhip_pose_error_diameter_host.argtypes = [C.POINTER(PoseBank), C.c_void_p]
+        L.slhip_pose_error.argtypes = [C.c_void_p, C.POINTER(PoseBank), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.POINTER(PoseErrorOut), C.c_void_p]
+        L.slhip_pose_error_host.argtypes = [C.c_void_p, C.POINTER(PoseBank), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                            C.c_uint32, C.POINTER(PoseErrorOut)]
+        L.slhip_pose_error_timing_enable.argtypes = [C.c_int]
+        L.slhip_pose_error_timings.argtypes = [C.POINTER(C.c_float * 2)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

@@ -521,6 +521,24 @@ class SceneBatch:
         return object_regions.label(buffers.instance[:B], buffers.coord[:B], self.d_objects[s0 * nb:(s0 + B) * nb], bank,
                                     n_objects=self.n_objects, **kw)
 
+    def pose_errors(self, estimates, bank, chunk=None, **kw):
+        """sl.pose_error.evaluate of pose estimates against the batch's own ground truth: its `object_to_camera`, its object
+        records (read in place) and its intrinsics.  `estimates`: float32 [B, O, Hy, 3, 4] or [B, O, 3, 4] for all scenes of the
+        batch, or with `chunk` for the scenes of that render chunk.  `bank`: a ModelBank of the batch's table
+        (sl.pose_error.bank(table, ...)).  `kw`: outputs.  Needs place(object_to_camera=True) for the view last placed."""
+        from . import pose_error
+
+        for name in ("intrinsics", "object_to_camera", "objects"):
+            if name in kw:
+                raise TypeError("SceneBatch.pose_errors sets `%s` itself" % name)
+        if self.object_to_camera is None or not self._object_to_camera_placed:
+            raise RuntimeError("SceneBatch.pose_errors needs object_to_camera of the view last placed: call "
+                               "place(object_to_camera=True) (the last place() did not keep it)")
+        s0, B = (0, self.n_scenes) if chunk is None else self._chunk_range(chunk)
+        nb = self.n_objects * _abi.SYNTH_OBJECT_DTYPE.itemsize
+        return pose_error.evaluate(self.object_to_camera[s0:s0 + B], estimates, self.d_objects[s0 * nb:(s0 + B) * nb], bank,
+                                   self.intrinsics(), **kw)
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

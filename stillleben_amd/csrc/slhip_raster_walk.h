@@ -84,6 +84,14 @@ struct Walk {
         row[0] += sy[0]; row[1] += sy[1]; row[2] += sy[2];
         e[0] = row[0]; e[1] = row[1]; e[2] = row[2];
     }
+    // n rows down in the same column (n >= 0): the strided walk of a pass in which every lane owns one texel of every n-th row
+    // (k_vis_fill).  Carried in I = long long there: e_i is at most 2^55 in magnitude for vertices that snap() bounds by 2^26
+    // and a pixel centre below 2^24, and a step of up to 2^16 rows at most 2^51.
+    SLHIP_RW_HD void rows_down(int n)
+    {
+        row[0] += I(n) * sy[0]; row[1] += I(n) * sy[1]; row[2] += I(n) * sy[2];
+        e[0] = row[0]; e[1] = row[1]; e[2] = row[2];
+    }
     // all three biased values >= 0, i.e. the sign bit of their OR is clear
     SLHIP_RW_HD bool inside() const { return (e[0] | e[1] | e[2]) >= I(0); }
     // e_i of the current texel: the numerator of barycentric i over area2

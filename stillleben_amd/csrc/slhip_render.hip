@@ -2,6 +2,8 @@
 // RenderPass of the reference (src/render_pass.cpp:303-796 + src/shaders/render_shader.*).
 //
 // Design (see DESIGN.md "Render half"):
+//   k_vis_fill initialises the visibility buffer: one lane per pixel stores the smallest key of the scene's fill draws (the
+//              background plane: few triangles, most of the picture) or "empty" -- no clear, no atomic for those pixels.
 //   k_raster   one thread per triangle of a chunk (scene/draw are workgroup-uniform).  Vertex
 //              transform chain, near clipping, 1/256-px snapping, exact integer edge functions.
 //              Small triangles are resolved by the owning thread with a 64-bit atomicMin on the
@@ -687,6 +689,18 @@ __device__ __forceinline__ void tex_rect_bilinear(const uint8_t* __restrict__ te
 // ---------------------------------------------------------------------------------------------
 // fragment emission
 // ---------------------------------------------------------------------------------------------
+// The visibility key of a covered pixel with screen-space barycentrics l: depth, depth range test, 24-bit depth | primitive.
+// False if the fragment is outside the depth range or at the far plane.  (MainTarget::emit and k_vis_fill: one key, two writers.)
+__device__ __forceinline__ bool fragment_key(const Setup& t, const float* l, unsigned prim, unsigned long long& key)
+{
+    const float z = interp(l, t.z[0], t.z[1], t.z[2]);
+    if (!(z >= 0.0f && z <= 1.0f)) return false;
+    const unsigned d24 = depth24(z);
+    if (d24 >= 0xFFFFFFu) return false;   // GL_LESS against the cleared depth 1.0: a fragment AT the far plane loses (R6)
+    key = ((unsigned long long)d24 << 32) | prim;
+    return true;
+}
+
 struct MainTarget {
     unsigned long long* vis;  // scene's [H,W] keys
     const float* peel;        // scene's [H,W,4] previous objectCoordinates or nullptr
@@ -705,11 +719,8 @@ struct MainTarget {
 
     __device__ __forceinline__ void emit(const Setup& t, int px, int py, const float* l) const
     {
-        const float z = interp(l, t.z[0], t.z[1], t.z[2]);
-        if (!(z >= 0.0f && z <= 1.0f)) return;
-        const unsigned d24 = depth24(z);
-        if (d24 >= 0xFFFFFFu) return;   // GL_LESS against the cleared depth 1.0: a fragment AT the far plane loses (R6)
-        const unsigned long long key = ((unsigned long long)d24 << 32) | prim;
+        unsigned long long key;
+        if (!fragment_key(t, l, prim, key)) return;
         unsigned long long* slot = vis + (size_t)py * W + px;
         // monotone pre-test only where the (rare, expensive) discard tests follow: keys only ever
         // decrease, so a stale read is conservative.  The plain path fires the atomic without
@@ -904,6 +915,39 @@ __device__ __forceinline__ void raster_or_enqueue(const Setup& t, const Target& 
 //                  vertex (`screen`), without a division;
 //   kAttr = true:  chunks whose fragments may be discarded before the depth write (alpha test against the base texture,
 //                  depth peeling): barycentrics, texture coordinates and camera z per fragment.
+//
+// FILL DRAWS.  The background plane covers most of a picture, has one writer per pixel and is known before any object is drawn:
+// k_vis_fill, the pass that initialises the keys, evaluates such triangles per pixel and STORES the smallest key instead of
+// kVisEmpty -- no queue entry, no tile of k_large, no atomic on a cleared key.  A fill draw is a plain draw (no discard test
+// before the depth write) of at most two triangles in a scene whose plain draws of at most two triangles have at most
+// kFillMaxTris triangles together (a scene made of a thousand quads has none: every one of them would be tested at every
+// pixel); with depth peeling there is none.  fill_draw() is the one verdict: k_vis_fill draws exactly the draws whose chunks
+// raster_chunk<false> leaves alone.  Everything it reads is uniform for the caller's block (scalar loads), and only a block
+// whose own draw is plain and small counts the scene's other draws.
+constexpr unsigned kFillMaxTris = 4;
+__device__ __forceinline__ bool fill_plain(unsigned flags, unsigned n_tris)
+{
+    return !((flags & SLHIP_DRAW_ALPHA_TEST) && (flags & SLHIP_DRAW_HAS_BASE_TEX)) && n_tris <= 2u;
+}
+// flags, n_tris: those of draw d, which every caller holds already -- almost every draw is turned away by them, before anything
+// else is loaded (a block of k_raster<false> is a chain of dependent loads, and its time is the length of that chain)
+__device__ __forceinline__ bool fill_draw(const slhip_scene* sc, const slhip_draw* __restrict__ draws, unsigned d, unsigned flags,
+                                          unsigned n_tris, bool depth_peel)
+{
+    if (depth_peel || !fill_plain(flags, n_tris)) return false;
+    const unsigned begin = sc->draw_begin, end = sc->draw_end;
+    if (d < begin || d >= end) return false;
+    unsigned n = 0;
+#pragma unroll 2
+    for (unsigned j = begin; j < end; ++j) {
+        const unsigned f = draws[j].flags, t = draws[j].n_tris;
+        n += fill_plain(f, t) ? t : 0u;
+    }
+    return n <= kFillMaxTris;
+}
+
+// fill: bit 0 = the fill draws are k_vis_fill's, bit 1 = the flag word of the queue header tells k_raster<true> whether any chunk
+// is its own (slhip_tile_queue.h); 0 = neither (SLHIP_VIS_FILL, see slhip_render)
 template <bool kAttr>
 __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_pool& pool, const slhip_scene* __restrict__ scenes,
                                              const slhip_draw* __restrict__ draws,
@@ -911,14 +955,22 @@ __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_po
                                              const float* __restrict__ depth_peel,
                                              unsigned long long* __restrict__ vis, unsigned* queue,
                                              unsigned capacity, const float4* __restrict__ clipbuf,
-                                             const uint4* __restrict__ screen, int small_area, int wide)
+                                             const uint4* __restrict__ screen, int small_area, int wide, int fill)
 {
     const slhip_chunk ch = chunks[chunk];
     if (threadIdx.x >= ch.count) return;
     const slhip_scene* sc = scenes + ch.scene;
     const slhip_draw* dr = draws + ch.draw;
-    const bool alpha_test = (dr->flags & SLHIP_DRAW_ALPHA_TEST) && (dr->flags & SLHIP_DRAW_HAS_BASE_TEX);
-    if ((alpha_test || depth_peel != nullptr) != kAttr) return;      // block-uniform: the chunk is the other instantiation's
+    const unsigned draw_flags = dr->flags;
+    const bool alpha_test = (draw_flags & SLHIP_DRAW_ALPHA_TEST) && (draw_flags & SLHIP_DRAW_HAS_BASE_TEX);
+    if ((alpha_test || depth_peel != nullptr) != kAttr) {            // block-uniform: the chunk is the other instantiation's
+        if constexpr (!kAttr)
+            if ((fill & 2) && threadIdx.x == 0) atomicOr(queue + slhip_tq::kFlagWord, slhip_tq::kFlagDiscardChunks);
+        return;
+    }
+    if constexpr (!kAttr)
+        // (asked only of a chunk of one or two triangles, which every chunk of a fill draw is: no other chunk loads anything for it)
+        if ((fill & 1) && ch.count <= 2u && fill_draw(sc, draws, ch.draw, draw_flags, dr->n_tris, false)) return;   // block-uniform: k_vis_fill has drawn it
     const unsigned tri = ch.first_tri + threadIdx.x;
     const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
     const unsigned vi[3] = {ip[0], ip[1], ip[2]};
@@ -1023,10 +1075,146 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_raster(slhip_mesh_po
                                                 const float* __restrict__ depth_peel,
                                                 unsigned long long* __restrict__ vis, unsigned* queue,
                                                 unsigned capacity, const float4* __restrict__ clipbuf,
-                                                const uint4* __restrict__ screen, int small_area, int wide)
+                                                const uint4* __restrict__ screen, int small_area, int wide, int fill)
 {
+    // the plain instantiation, which has seen every chunk header, met none of this one's (a batch without an alpha-tested draw):
+    // nothing to skim for.  With depth peeling every chunk is this one's.
+    if constexpr (kAttr)
+        if ((fill & 2) && depth_peel == nullptr && queue[slhip_tq::kFlagWord] == 0u) return;
     for (unsigned c = blockIdx.x; c < n_chunks; c += gridDim.x)
-        raster_chunk<kAttr>(c, pool, scenes, draws, chunks, W, H, depth_peel, vis, queue, capacity, clipbuf, screen, small_area, wide);
+        raster_chunk<kAttr>(c, pool, scenes, draws, chunks, W, H, depth_peel, vis, queue, capacity, clipbuf, screen, small_area, wide, fill);
+}
+
+// k_vis_fill: the pass that initialises the visibility keys.  Every pixel of every scene is owned by one lane, which stores
+// the smallest key of the scene's fill triangles there (fill_draw() above), or kVisEmpty: one plain 8-byte store per pixel, and
+// nothing of an earlier call survives.  geometry == 0 (no chunks, or depth peeling): a pure clear.
+//   Placement: a block owns a strip of 64 columns and `rows_per_block` rows of one scene; wave w of its four takes the rows
+//   w, w + 4, ... of the strip, lane == column, so a wave stores 512 contiguous bytes.  All blocks of a scene share an XCD
+//   (scene_block).
+//   Set-up: thread i sets up fill triangle i of the scene exactly as k_large would (window coordinates where all corners are in
+//   front of the near plane, else the near clip and up to two sub-triangles) and leaves it in LDS.
+//   Per pixel: the biased edge values at the lane's first row by products, once per triangle and kFillRows rows, then stepped
+//   four rows down (slhip_raster::Walk::rows_down: the integers of cover<long long>); the key is MainTarget::emit's.
+__device__ __forceinline__ bool scene_block(unsigned blocks_per_scene, unsigned n_scenes, unsigned& scene, unsigned& blk);   // below
+constexpr int kFillRows = 8;    // rows whose keys a lane holds in registers while it goes through the triangles
+struct FillList {
+    Setup t[2 * kFillMaxTris];
+    unsigned prim[2 * kFillMaxTris];
+    unsigned tri[kFillMaxTris][2];   // draw, triangle
+    unsigned n_tri, n_sub;
+};
+__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+// a Setup that is the same in every lane, told to the compiler (scalar registers)
+__device__ __forceinline__ void uniform_setup(const Setup& s, Setup& t)
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        t.X[i] = uniform_i(s.X[i]); t.Y[i] = uniform_i(s.Y[i]); t.bias[i] = uniform_i(s.bias[i]);
+        t.z[i] = uniform_f(s.z[i]); t.invw[i] = uniform_f(s.invw[i]);
+    }
+    t.area2 = (long long)(((unsigned long long)(unsigned)uniform_i((int)(s.area2 >> 32)) << 32) | (unsigned)uniform_i((int)s.area2));
+    t.flipped = uniform_i(s.flipped); t.narrow = uniform_i(s.narrow);
+    t.xmin = uniform_i(s.xmin); t.xmax = uniform_i(s.xmax); t.ymin = uniform_i(s.ymin); t.ymax = uniform_i(s.ymax);
+}
+
+__global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_vis_fill(slhip_mesh_pool pool, const slhip_scene* __restrict__ scenes,
+                                                  const slhip_draw* __restrict__ draws, unsigned n_scenes, int W, int H,
+                                                  unsigned rows_per_block, int geometry, unsigned long long* __restrict__ vis,
+                                                  const float4* __restrict__ clipbuf, const uint4* __restrict__ screen)
+{
+    __shared__ FillList s;
+    const unsigned col_strips = ((unsigned)W + 63u) >> 6, row_strips = ((unsigned)H + rows_per_block - 1u) / rows_per_block;
+    unsigned scene, blk;
+    if (!scene_block(col_strips * row_strips, n_scenes, scene, blk)) return;
+    if (threadIdx.x == 0) { s.n_tri = 0u; s.n_sub = 0u; }
+    __syncthreads();
+    if (geometry) {
+        const slhip_scene* sc = scenes + scene;
+        for (unsigned d = sc->draw_begin + threadIdx.x; d < sc->draw_end; d += blockDim.x) {
+            const unsigned n = draws[d].n_tris;                      // all fill draws together: at most kFillMaxTris
+            if (fill_draw(sc, draws, d, draws[d].flags, n, false)) {
+                const unsigned base = atomicAdd(&s.n_tri, n);
+                for (unsigned k = 0; k < n; ++k) { s.tri[base + k][0] = d; s.tri[base + k][1] = k; }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < s.n_tri) {
+            const slhip_draw* dr = draws + s.tri[threadIdx.x][0];
+            const unsigned tri = s.tri[threadIdx.x][1];
+            const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
+            const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
+            Setup t;
+            if (screen_all_inside(s0, s1, s2)) {
+                if (setup_from_screen(s0, s1, s2, W, H, t)) {
+                    const unsigned slot = atomicAdd(&s.n_sub, 1u);
+                    s.t[slot] = t; s.prim[slot] = dr->prim_base + tri;
+                }
+            } else {
+                ClipVert cv[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float4 c4 = clipbuf[dr->clip_base + ip[k]];
+                    cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
+                    cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
+                }
+                ClipVert poly[4];
+                const int n = clip_near(cv, poly);
+#pragma unroll
+                for (int sub = 0; sub < 2; ++sub) {
+                    if (sub >= n - 2) break;
+                    if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
+                    const unsigned slot = atomicAdd(&s.n_sub, 1u);
+                    s.t[slot] = t; s.prim[slot] = dr->prim_base + tri;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // (the order of the sub-triangles in the list is that of the LDS atomics; the minimum does not depend on it)
+    const int n_sub = uniform_i((int)s.n_sub);
+    const unsigned cs = blk % col_strips, rs = blk / col_strips;
+    const int x0 = (int)(cs << 6), px = x0 + (int)(threadIdx.x & 63u);
+    const int wave = uniform_i((int)(threadIdx.x >> 6));
+    const int row_begin = (int)(rs * rows_per_block), row_end = min(H, row_begin + (int)rows_per_block);
+    unsigned long long* out = vis + (size_t)scene * W * H;
+    for (int r0 = row_begin; r0 < row_end; r0 += 4 * kFillRows) {
+        const int py0 = r0 + wave, py_last = py0 + 4 * (kFillRows - 1);    // the lane's rows: py0 + 4 k
+        unsigned long long key[kFillRows];
+#pragma unroll
+        for (int k = 0; k < kFillRows; ++k) key[k] = kVisEmpty;
+        for (int i = 0; i < n_sub; ++i) {
+            // the wave's texels are outside the triangle's pixel box: nothing to evaluate
+            if (x0 + 63 < uniform_i(s.t[i].xmin) || x0 > uniform_i(s.t[i].xmax) || py_last < uniform_i(s.t[i].ymin) ||
+                py0 > uniform_i(s.t[i].ymax))
+                continue;
+            Setup t;
+            uniform_setup(s.t[i], t);
+            const unsigned prim = (unsigned)uniform_i((int)s.prim[i]);
+            slhip_raster::Walk<long long> w;
+            w.start(t.X, t.Y, t.flipped, t.bias, px, py0);
+            const float fa = (float)t.area2;
+            const bool in_columns = px >= t.xmin && px <= t.xmax;
+#pragma unroll
+            for (int k = 0; k < kFillRows; ++k) {
+                const int py = py0 + 4 * k;
+                if (in_columns && py >= t.ymin && py <= t.ymax && w.inside()) {
+                    float l[3];
+                    l[0] = (float)w.numerator(0) / fa;
+                    l[1] = (float)w.numerator(1) / fa;
+                    l[2] = (float)w.numerator(2) / fa;
+                    unsigned long long kk;
+                    if (fragment_key(t, l, prim, kk)) key[k] = min(key[k], kk);
+                }
+                w.rows_down(4);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kFillRows; ++k) {
+            const int py = py0 + 4 * k;
+            if (px < W && py < row_end) out[(size_t)py * W + px] = key[k];
+        }
+    }
 }
 
 // k_large: one wave per (triangle, 8x8 tile); lane == pixel.  Every wave takes a CONTIGUOUS run of
@@ -2801,17 +2989,31 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
 
     // main pass: visibility
     mark(2, stream);
-    SLHIP_CHECK(hipMemsetAsync(scratch->d_vis, 0xFF, (size_t)n_scenes * P * 8, stream));
+    // developer knob, read at every call like SLHIP_RASTER_WIDE: bit 0 = k_vis_fill initialises the keys and draws the fill draws
+    // (else: a memset, and the fill draws go through k_raster, the queue and k_large), bit 1 = k_raster<true> leaves at once when
+    // k_raster<false> met no chunk of its kind (else: it skims the chunk list).  Default 3; 0 = the in-library reference of both.
+    // SLHIP_RASTER_SMALL says which walker takes a triangle -- 0: every triangle to the tile-queue kernels, 2^30: every one in
+    // place -- and the fill pass is a third walker: where that knob is set and this one is not, the fill draws obey it too
+    const int vis_fill = getenv("SLHIP_VIS_FILL") ? atoi(getenv("SLHIP_VIS_FILL")) : (getenv("SLHIP_RASTER_SMALL") ? 2 : 3);
+    if (vis_fill & 1) {
+        const unsigned rows_per_block = 96u;    // a multiple of 4 * kFillRows: three passes of a block over its triangles
+        const unsigned strips = (((unsigned)W + 63u) >> 6) * (((unsigned)H + rows_per_block - 1u) / rows_per_block);
+        k_vis_fill<<<strips * 8u * ((n_scenes + 7u) / 8u), 256, 0, stream>>>(
+            *pool, d_scenes, d_draws, n_scenes, W, H, rows_per_block, n_chunks > 0 && !d_depth_peel ? 1 : 0,
+            reinterpret_cast<unsigned long long*>(scratch->d_vis), clipbuf, screen);
+        SLHIP_LAUNCH_CHECK();
+    } else
+        SLHIP_CHECK(hipMemsetAsync(scratch->d_vis, 0xFF, (size_t)n_scenes * P * 8, stream));
     SLHIP_CHECK(hipMemsetAsync(scratch->d_queue, 0, 16, stream));
     if (n_chunks > 0) {
         // with depth peeling every chunk takes the discard-testing form; without it only the alpha-tested draws do
         if (!d_depth_peel)
             k_raster<false><<<n_chunks, 256, 0, stream>>>(*pool, d_scenes, d_draws, d_chunks, n_chunks, W, H, d_depth_peel,
                                                           reinterpret_cast<unsigned long long*>(scratch->d_vis),
-                                                          scratch->d_queue, scratch->queue_capacity, clipbuf, screen, raster_small, raster_wide);
+                                                          scratch->d_queue, scratch->queue_capacity, clipbuf, screen, raster_small, raster_wide, vis_fill);
         k_raster<true><<<d_depth_peel ? n_chunks : min(n_chunks, 4096u), 256, 0, stream>>>(
             *pool, d_scenes, d_draws, d_chunks, n_chunks, W, H, d_depth_peel, reinterpret_cast<unsigned long long*>(scratch->d_vis),
-            scratch->d_queue, scratch->queue_capacity, clipbuf, screen, raster_small, raster_wide);
+            scratch->d_queue, scratch->queue_capacity, clipbuf, screen, raster_small, raster_wide, vis_fill);
         mark(3, stream);
         k_large<<<2048, 256, 0, stream>>>(*pool, d_scenes, d_draws, W, H,
                                           reinterpret_cast<unsigned long long*>(scratch->d_vis), scratch->d_queue,

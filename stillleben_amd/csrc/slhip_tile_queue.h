@@ -10,6 +10,9 @@
 //                      1 | n_tiles << 32 with one atomic and so learns its entry index and the first tile of its range; as one
 //                      atomic hands out both, the entries are ordered by tile_base.
 //   header word 2:     set once a tile reservation carried out of 32 bits (below).
+//   header word 3:     not the queue's: a flag word of the pass that owns the queue, zeroed with the header.  The visibility pass
+//                      raises kFlagDiscardChunks in it when k_raster<false> meets a chunk of the discard-testing instantiation,
+//                      and every block of k_raster<true> leaves at once while it is zero.  plan_of() never sees it.
 // A triangle whose entry index is beyond the capacity is walked in place by its producer; its tile range stays reserved with no
 // entry behind it (such ranges are the last of the queue).  A triangle whose range would carry out of 32 bits is walked in place
 // as well and leaves a void entry (no tiles); it raises header word 2, because the tile counter has wrapped for every producer
@@ -32,6 +35,8 @@ namespace slhip_tq {
 
 constexpr unsigned kHeaderWords = 4;      // 16 bytes
 constexpr unsigned kUnitsPerEntry = 2;    // 32 bytes
+constexpr unsigned kFlagWord = 3;         // header word 3 (above)
+constexpr unsigned kFlagDiscardChunks = 1u;
 
 struct Entry {
     unsigned draw;       // global draw index

@@ -337,6 +337,74 @@ __device__ __forceinline__ int clip_near(const ClipVert* in, ClipVert* out)
     }
 }
 
+// HOW A TRIANGLE OF A DRAW BECOMES A Setup.  Every pass that rasterises a triangle of the picture or finds it again per pixel
+// takes it through the definitions below, so that all of them see the same Setup bit for bit: the visibility pass
+// (raster_chunk, k_vis_fill, k_large), the shading pass (k_shade) and the silhouette pass (k_os_raster, k_os_large).
+
+// The triangle's clip positions, as k_vertex_xform (MFMA) wrote them -- the one place that reads `clipbuf`.  vi: its three
+// vertex indices; the corners' barycentrics are the unit vectors, or zero where the caller has no use for them.
+template <bool kUnitBary>
+__device__ __forceinline__ void clip_tri(const float4* clipbuf, unsigned clip_base, const unsigned* vi, ClipVert* cv)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float4 c4 = clipbuf[clip_base + vi[k]];
+        cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) cv[k].bary[j] = kUnitBary && j == k ? 1.0f : 0.0f;
+    }
+}
+
+// The rule per triangle.  s0..s2: the corners' window-coordinate records.  All three in front of the near plane (clip_near()
+// would hand the triangle through): the set-up from those records, without a division, as sub 0 with the unit barycentrics.
+// Otherwise the near clip and up to two sub-triangles, each with the barycentrics of its corners w.r.t. the original.
+// f(sub, t, b0, b1, b2) is called for every Setup inside the W x H target; it returns false to stop.
+template <bool kUnitBary, class F>
+__device__ __forceinline__ void for_each_setup(const uint4& s0, const uint4& s1, const uint4& s2, const float4* clipbuf,
+                                               unsigned clip_base, const unsigned* vi, int W, int H, F&& f)
+{
+    if (screen_all_inside(s0, s1, s2)) {
+        const float e0[3] = {1.0f, 0.0f, 0.0f}, e1[3] = {0.0f, 1.0f, 0.0f}, e2[3] = {0.0f, 0.0f, 1.0f};
+        Setup t;
+        if (setup_from_screen(s0, s1, s2, W, H, t)) f(0, t, e0, e1, e2);
+        return;
+    }
+    ClipVert cv[3], poly[4];
+    clip_tri<kUnitBary>(clipbuf, clip_base, vi, cv);
+    const int n = clip_near(cv, poly);
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {   // n <= 4: at most two sub-triangles; unrolled so that poly[] keeps static indices
+        if (sub >= n - 2) break;
+        Setup t;
+        if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
+        if (!f(sub, t, poly[0].bary, poly[sub + 1].bary, poly[sub + 2].bary)) break;
+    }
+}
+
+// The rule per entry of the large-triangle queue (raster_or_enqueue wrote it): the one Setup that for_each_setup() passed as
+// (tri, sub).  False: skip the entry.
+__device__ __forceinline__ bool entry_setup(const slhip_tq::Entry& en, const slhip_draw* dr, const slhip_mesh_pool& pool,
+                                            const uint4* screen, const float4* clipbuf, int W, int H,
+                                            Setup& t, unsigned& tri)
+{
+    tri = en.tri_sub & 0x7FFFFFFFu;
+    const int sub = (int)(en.tri_sub >> 31);
+    const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
+    const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
+    const bool cached = screen_all_inside(s0, s1, s2);
+    if (cached && (sub != 0 || !setup_from_screen(s0, s1, s2, W, H, t))) return false;
+    if (!cached) {
+        ClipVert cv[3], poly[4];
+        clip_tri<false>(clipbuf, dr->clip_base, ip, cv);
+        const int n = clip_near(cv, poly);
+        if (sub > n - 3) return false;
+        const ClipVert& pb = sub == 0 ? poly[1] : poly[2];
+        const ClipVert& pc = sub == 0 ? poly[2] : poly[3];
+        if (!setup_tri(poly[0].clip, pb.clip, pc.clip, W, H, t)) return false;
+    }
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // vertex stage (render_shader.vert:57-95)
 // ---------------------------------------------------------------------------------------------
@@ -701,6 +769,66 @@ __device__ __forceinline__ bool fragment_key(const Setup& t, const float* l, uns
     return true;
 }
 
+// An alpha-tested draw: fragments whose base-texture alpha is below the cutoff are discarded before the depth write.
+__device__ __forceinline__ bool draw_alpha_tested(unsigned flags)
+{
+    return (flags & SLHIP_DRAW_ALPHA_TEST) && (flags & SLHIP_DRAW_HAS_BASE_TEX);
+}
+
+// The alpha discard of a fragment -- the one definition: the visibility pass (MainTarget) and the silhouette pass (StatsTarget of
+// slhip_render_stats.inc) must keep and drop the same fragments.
+struct AlphaTest {
+    const float* uv;     // [3][2] of the ORIGINAL vertices
+    const float* bary;   // [3][3] barycentrics of the sub-triangle vertices w.r.t. the original
+    const uint8_t* pool_tex;   // texel pool, nullptr = no alpha test
+    unsigned tex;              // byte offset of the base-colour texture in the pool
+    int tex_w, tex_h;
+    unsigned tex_sampler;
+    float base_alpha, alpha_cutoff;
+
+    // uvs: [6], the caller's storage for the triangle's texture coordinates
+    static __device__ __forceinline__ AlphaTest from_draw(const slhip_mesh_pool& pool, const slhip_draw* __restrict__ dr, const unsigned* vi,
+                                                          float* uvs)
+    {
+        AlphaTest a;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float2 uv = reinterpret_cast<const float2*>(pool.d_uv)[dr->vtx_base + vi[k]];
+            uvs[2 * k] = uv.x; uvs[2 * k + 1] = uv.y;
+        }
+        a.uv = uvs; a.bary = nullptr;
+        a.pool_tex = pool.d_tex; a.tex = dr->tex_offset;
+        a.tex_w = (int)dr->tex_w; a.tex_h = (int)dr->tex_h;
+        a.tex_sampler = dr->tex_sampler[0];
+        a.base_alpha = dr->base_color[3];
+        a.alpha_cutoff = dr->alpha_cutoff;
+        return a;
+    }
+    // perspective-correct barycentrics b (w.r.t. the original triangle) of a covered pixel with screen-space barycentrics l
+    __device__ __forceinline__ void persp_bary(const Setup& t, const float* l, float* b) const
+    {
+        const float pw0 = l[0] * t.invw[0], pw1 = l[1] * t.invw[1], pw2 = l[2] * t.invw[2];
+        const float sw = (pw0 + pw1) + pw2;
+        const float bs[3] = {pw0 * (1.0f / sw), pw1 * (1.0f / sw), pw2 * (1.0f / sw)};
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            b[k] = fmaf(bs[2], bary[6 + k], fmaf(bs[1], bary[3 + k], bs[0] * bary[k]));
+    }
+    // b: persp_bary() of the pixel.  The texture footprint comes from the barycentrics one pixel to the right / below.
+    __device__ __forceinline__ bool discards(const Setup& t, int px, int py, const float* b) const
+    {
+        const float u = interp(b, uv[0], uv[2], uv[4]);
+        const float v = interp(b, uv[1], uv[3], uv[5]);
+        float bx[3], by[3];
+        bary_at(t, bary, bary + 3, bary + 6, px + 1, py, bx);
+        bary_at(t, bary, bary + 3, bary + 6, px, py + 1, by);
+        float tc[4];
+        tex_sample(pool_tex, tex, tex_w, tex_h, tex_sampler, u, v, interp(bx, uv[0], uv[2], uv[4]) - u, interp(bx, uv[1], uv[3], uv[5]) - v,
+                   interp(by, uv[0], uv[2], uv[4]) - u, interp(by, uv[1], uv[3], uv[5]) - v, tc);
+        return base_alpha * tc[3] < alpha_cutoff;
+    }
+};
+
 struct MainTarget {
     unsigned long long* vis;  // scene's [H,W] keys
     const float* peel;        // scene's [H,W,4] previous objectCoordinates or nullptr
@@ -709,13 +837,17 @@ struct MainTarget {
     // for the (rare) discard tests that run before the depth write
     bool need_attr;
     const float* camz;   // [3] camera z of the ORIGINAL vertices
-    const float* bary;   // [3][3] barycentrics of the sub-triangle vertices w.r.t. the original
-    const float* uv;     // [3][2]
-    const uint8_t* pool_tex;   // texel pool, nullptr = no alpha test
-    unsigned tex;              // byte offset of the base-colour texture in the pool
-    int tex_w, tex_h;
-    unsigned tex_sampler;
-    float base_alpha, alpha_cutoff;
+    AlphaTest alpha;     // (its `bary` serves the peel test too)
+
+    // no discard test: depth and primitive id only
+    static __device__ __forceinline__ MainTarget plain(unsigned long long* vis, int W, unsigned prim)
+    {
+        MainTarget tgt;
+        tgt.vis = vis; tgt.peel = nullptr; tgt.W = W; tgt.prim = prim;
+        tgt.need_attr = false; tgt.camz = nullptr;
+        tgt.alpha.pool_tex = nullptr;
+        return tgt;
+    }
 
     __device__ __forceinline__ void emit(const Setup& t, int px, int py, const float* l) const
     {
@@ -727,28 +859,13 @@ struct MainTarget {
         // waiting on a read (a memory round trip per fragment costs more than a lost atomic).
         if (need_attr && __builtin_nontemporal_load(slot) <= key) return;
         if (need_attr) {
-            const float pw0 = l[0] * t.invw[0], pw1 = l[1] * t.invw[1], pw2 = l[2] * t.invw[2];
-            const float sw = (pw0 + pw1) + pw2;
-            const float bs[3] = {pw0 * (1.0f / sw), pw1 * (1.0f / sw), pw2 * (1.0f / sw)};
             float b[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                b[k] = fmaf(bs[2], bary[6 + k], fmaf(bs[1], bary[3 + k], bs[0] * bary[k]));
+            alpha.persp_bary(t, l, b);
             if (peel) {
                 const float cz = interp(b, camz[0], camz[1], camz[2]);
                 if (cz - 0.00001f <= peel[4 * ((size_t)py * W + px) + 3]) return;
             }
-            if (pool_tex) {
-                const float u = interp(b, uv[0], uv[2], uv[4]);
-                const float v = interp(b, uv[1], uv[3], uv[5]);
-                float bx[3], by[3];
-                bary_at(t, bary, bary + 3, bary + 6, px + 1, py, bx);
-                bary_at(t, bary, bary + 3, bary + 6, px, py + 1, by);
-                float tc[4];
-                tex_sample(pool_tex, tex, tex_w, tex_h, tex_sampler, u, v, interp(bx, uv[0], uv[2], uv[4]) - u, interp(bx, uv[1], uv[3], uv[5]) - v,
-                           interp(by, uv[0], uv[2], uv[4]) - u, interp(by, uv[1], uv[3], uv[5]) - v, tc);
-                if (base_alpha * tc[3] < alpha_cutoff) return;
-            }
+            if (alpha.pool_tex && alpha.discards(t, px, py, b)) return;
         }
         atomicMin(slot, key);
     }
@@ -905,6 +1022,42 @@ __device__ __forceinline__ void raster_or_enqueue(const Setup& t, const Target& 
     if (in_place) raster_bbox(t, tgt, wide);
 }
 
+// The walk of a triangle whose fragments may be discarded before the depth write (raster_chunk<true>, k_os_raster<true>): such
+// triangles stay in place, since the discard tests need per-vertex data that only this thread holds.
+// One set-up sub-triangle whose corners have the barycentrics b0..b2 w.r.t. the original: every pixel of its box; tgt.emit()
+// finds the nine barycentrics in tgt.alpha.bary.
+template <class Target>
+__device__ __forceinline__ void walk_attr_sub(const Setup& t, const float* b0, const float* b1, const float* b2, Target& tgt)
+{
+    float bary[9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        bary[k] = b0[k];
+        bary[3 + k] = b1[k];
+        bary[6 + k] = b2[k];
+    }
+    tgt.alpha.bary = bary;
+    for (int py = t.ymin; py <= t.ymax; ++py)
+        for (int px = t.xmin; px <= t.xmax; ++px) {
+            float l[3];
+            if (coverage(t, px, py, l)) tgt.emit(t, px, py, l);
+        }
+}
+// The triangle with the clip positions and unit barycentrics cv: near clip, set-up and walk of up to two sub-triangles.
+template <class Target>
+__device__ __forceinline__ void walk_attr_tri(const ClipVert* cv, int W, int H, Target& tgt)
+{
+    ClipVert poly[4];
+    const int n = clip_near(cv, poly);
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {   // unrolled: static indices into poly[]
+        if (sub >= n - 2) break;
+        Setup t;
+        if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
+        walk_attr_sub(t, poly[0].bary, poly[sub + 1].bary, poly[sub + 2].bary, tgt);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // k_raster: main pass, one thread per triangle
 // ---------------------------------------------------------------------------------------------
@@ -927,7 +1080,7 @@ __device__ __forceinline__ void raster_or_enqueue(const Setup& t, const Target& 
 constexpr unsigned kFillMaxTris = 4;
 __device__ __forceinline__ bool fill_plain(unsigned flags, unsigned n_tris)
 {
-    return !((flags & SLHIP_DRAW_ALPHA_TEST) && (flags & SLHIP_DRAW_HAS_BASE_TEX)) && n_tris <= 2u;
+    return !draw_alpha_tested(flags) && n_tris <= 2u;
 }
 // flags, n_tris: those of draw d, which every caller holds already -- almost every draw is turned away by them, before anything
 // else is loaded (a block of k_raster<false> is a chain of dependent loads, and its time is the length of that chain)
@@ -962,7 +1115,7 @@ __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_po
     const slhip_scene* sc = scenes + ch.scene;
     const slhip_draw* dr = draws + ch.draw;
     const unsigned draw_flags = dr->flags;
-    const bool alpha_test = (draw_flags & SLHIP_DRAW_ALPHA_TEST) && (draw_flags & SLHIP_DRAW_HAS_BASE_TEX);
+    const bool alpha_test = draw_alpha_tested(draw_flags);
     if ((alpha_test || depth_peel != nullptr) != kAttr) {            // block-uniform: the chunk is the other instantiation's
         if constexpr (!kAttr)
             if ((fill & 2) && threadIdx.x == 0) atomicOr(queue + slhip_tq::kFlagWord, slhip_tq::kFlagDiscardChunks);
@@ -975,29 +1128,18 @@ __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_po
     const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
     const unsigned vi[3] = {ip[0], ip[1], ip[2]};
     const size_t P = (size_t)W * H;
-    MainTarget tgt;
-    tgt.vis = vis + (size_t)ch.scene * P;
-    tgt.W = W;
-    tgt.prim = dr->prim_base + tri;
-    tgt.need_attr = kAttr;
-    tgt.peel = nullptr;
-    tgt.pool_tex = nullptr;
+    MainTarget tgt = MainTarget::plain(vis + (size_t)ch.scene * P, W, dr->prim_base + tri);
 
     if constexpr (!kAttr) {
-        tgt.camz = nullptr; tgt.uv = nullptr; tgt.bary = nullptr;
         const uint4 s0 = screen[dr->clip_base + vi[0]], s1 = screen[dr->clip_base + vi[1]], s2 = screen[dr->clip_base + vi[2]];
+        // for_each_setup(), spelled out: with the call this phase alone is faster, the benchmark 0.3 - 0.8 % slower (profiles/r14)
         if (screen_all_inside(s0, s1, s2)) {     // clip_near() would hand the triangle through
             Setup t;
             if (setup_from_screen(s0, s1, s2, W, H, t)) raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri, ch.scene, small_area, wide);
             return;
         }
         ClipVert cv[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float4 c4 = clipbuf[dr->clip_base + vi[k]];   // written by k_vertex_xform (MFMA)
-            cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-            cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;   // (not needed here)
-        }
+        clip_tri<false>(clipbuf, dr->clip_base, vi, cv);
         ClipVert poly[4];
         const int n = clip_near(cv, poly);
 #pragma unroll
@@ -1009,57 +1151,30 @@ __device__ __forceinline__ void raster_chunk(unsigned chunk, const slhip_mesh_po
         }
     } else {
         ClipVert cv[3];
+        clip_tri<true>(clipbuf, dr->clip_base, vi, cv);
         float camz[3] = {0.0f, 0.0f, 0.0f};
+        if (depth_peel) {  // camera z of the vertices (shader chain) for the depth-peel test
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float4 c4 = clipbuf[dr->clip_base + vi[k]];   // written by k_vertex_xform (MFMA)
-            cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-            if (depth_peel) {  // camera z of the vertex (shader chain) for the depth-peel test
+            for (int k = 0; k < 3; ++k) {
                 float unused[4];
                 vertex_clip(pool, sc, dr, dr->vtx_base + vi[k], unused, camz[k]);
             }
-            cv[k].bary[0] = k == 0 ? 1.0f : 0.0f;
-            cv[k].bary[1] = k == 1 ? 1.0f : 0.0f;
-            cv[k].bary[2] = k == 2 ? 1.0f : 0.0f;
+            tgt.peel = depth_peel + 4 * (size_t)ch.scene * P;
         }
+        float uvs[6];
+        if (alpha_test) tgt.alpha = AlphaTest::from_draw(pool, dr, vi, uvs);
+        tgt.need_attr = true;
+        tgt.camz = camz;
+        // walk_attr_tri(cv, W, H, tgt), spelled out: through the call the kernel takes 129 VGPRs instead of 127 and loses its fourth
+        // wave per SIMD (profiles/r14)
         ClipVert poly[4];
         const int n = clip_near(cv, poly);
-        if (n == 0) return;
-        tgt.peel = depth_peel ? depth_peel + 4 * (size_t)ch.scene * P : nullptr;
-        float uvs[6] = {0, 0, 0, 0, 0, 0};
-        if (alpha_test) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float2 uv = reinterpret_cast<const float2*>(pool.d_uv)[dr->vtx_base + vi[k]];
-                uvs[2 * k] = uv.x; uvs[2 * k + 1] = uv.y;
-            }
-            tgt.pool_tex = pool.d_tex; tgt.tex = dr->tex_offset;
-            tgt.tex_w = (int)dr->tex_w; tgt.tex_h = (int)dr->tex_h;
-            tgt.tex_sampler = dr->tex_sampler[0];
-        }
-        tgt.camz = camz;
-        tgt.uv = uvs;
-        tgt.base_alpha = dr->base_color[3];
-        tgt.alpha_cutoff = dr->alpha_cutoff;
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             if (sub >= n - 2) break;
             Setup t;
             if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
-            float bary[9];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                bary[k] = poly[0].bary[k];
-                bary[3 + k] = poly[sub + 1].bary[k];
-                bary[6 + k] = poly[sub + 2].bary[k];
-            }
-            tgt.bary = bary;
-            // the discard tests need per-vertex data that only this thread holds: such triangles stay in place
-            for (int py = t.ymin; py <= t.ymax; ++py)
-                for (int px = t.xmin; px <= t.xmax; ++px) {
-                    float l[3];
-                    if (coverage(t, px, py, l)) tgt.emit(t, px, py, l);
-                }
+            walk_attr_sub(t, poly[0].bary, poly[sub + 1].bary, poly[sub + 2].bary, tgt);
         }
     }
 }
@@ -1091,8 +1206,7 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_raster(slhip_mesh_po
 //   Placement: a block owns a strip of 64 columns and `rows_per_block` rows of one scene; wave w of its four takes the rows
 //   w, w + 4, ... of the strip, lane == column, so a wave stores 512 contiguous bytes.  All blocks of a scene share an XCD
 //   (scene_block).
-//   Set-up: thread i sets up fill triangle i of the scene exactly as k_large would (window coordinates where all corners are in
-//   front of the near plane, else the near clip and up to two sub-triangles) and leaves it in LDS.
+//   Set-up: thread i sets up fill triangle i of the scene (for_each_setup) and leaves it in LDS.
 //   Per pixel: the biased edge values at the lane's first row by products, once per triangle and kFillRows rows, then stepped
 //   four rows down (slhip_raster::Walk::rows_down: the integers of cover<long long>); the key is MainTarget::emit's.
 __device__ __forceinline__ bool scene_block(unsigned blocks_per_scene, unsigned n_scenes, unsigned& scene, unsigned& blk);   // below
@@ -1144,30 +1258,11 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_vis_fill(slhip_mesh_
             const unsigned tri = s.tri[threadIdx.x][1];
             const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
             const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
-            Setup t;
-            if (screen_all_inside(s0, s1, s2)) {
-                if (setup_from_screen(s0, s1, s2, W, H, t)) {
-                    const unsigned slot = atomicAdd(&s.n_sub, 1u);
-                    s.t[slot] = t; s.prim[slot] = dr->prim_base + tri;
-                }
-            } else {
-                ClipVert cv[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float4 c4 = clipbuf[dr->clip_base + ip[k]];
-                    cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-                    cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
-                }
-                ClipVert poly[4];
-                const int n = clip_near(cv, poly);
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub) {
-                    if (sub >= n - 2) break;
-                    if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
-                    const unsigned slot = atomicAdd(&s.n_sub, 1u);
-                    s.t[slot] = t; s.prim[slot] = dr->prim_base + tri;
-                }
-            }
+            for_each_setup<false>(s0, s1, s2, clipbuf, dr->clip_base, ip, W, H, [&](int, const Setup& t, const float*, const float*, const float*) {
+                const unsigned slot = atomicAdd(&s.n_sub, 1u);
+                s.t[slot] = t; s.prim[slot] = dr->prim_base + tri;
+                return true;
+            });
         }
         __syncthreads();
     }
@@ -1235,34 +1330,9 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_large(slhip_mesh_poo
         if (!q.walk.tiles(en, k0, k1)) continue;
         Setup t;
         const slhip_draw* dr = draws + en.draw;
-        const unsigned tri = en.tri_sub & 0x7FFFFFFFu;
-        const int sub = (int)(en.tri_sub >> 31);
-        const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
-        ClipVert cv[3];
-        const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
-        const bool cached = screen_all_inside(s0, s1, s2);
-        if (cached && (sub != 0 || !setup_from_screen(s0, s1, s2, W, H, t))) continue;
-        if (!cached) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float4 c4 = clipbuf[dr->clip_base + ip[k]];
-                cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-                cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
-            }
-            ClipVert poly[4];
-            const int n = clip_near(cv, poly);
-            if (sub > n - 3) continue;
-            const ClipVert& pb = sub == 0 ? poly[1] : poly[2];
-            const ClipVert& pc = sub == 0 ? poly[2] : poly[3];
-            if (!setup_tri(poly[0].clip, pb.clip, pc.clip, W, H, t)) continue;
-        }
-        MainTarget tgt;
-        tgt.vis = vis + (size_t)en.scene_aux * W * H;
-        tgt.peel = nullptr;
-        tgt.W = W;
-        tgt.prim = dr->prim_base + tri;
-        tgt.need_attr = false;
-        tgt.pool_tex = nullptr;
+        unsigned tri;
+        if (!entry_setup(en, dr, pool, screen, clipbuf, W, H, t, tri)) continue;
+        const MainTarget tgt = MainTarget::plain(vis + (size_t)en.scene_aux * W * H, W, dr->prim_base + tri);
         TilePixels tp(en, k0, lane);
         for (unsigned k = k0; k < k1; ++k) {
             int px, py;
@@ -1805,6 +1875,30 @@ __device__ __forceinline__ bool scene_block(unsigned blocks_per_scene, unsigned 
     return scene < n_scenes;
 }
 
+// The last of a scene's draws whose first primitive id is <= prim, as an index into the scene's draws (its draw 0 starts at the
+// scene's primitive 0).  s_table: the first primitive ids of the scene's draws in LDS, kTable (a power of two) entries padded
+// with ~0: log2(kTable) halving steps.
+__device__ __forceinline__ unsigned table_draw_of_prim(const unsigned* s_table, unsigned kTable, unsigned prim)
+{
+    unsigned lo = 0u;
+#pragma unroll
+    for (unsigned step = kTable / 2; step > 0u; step >>= 1)
+        if (prim >= s_table[lo + step]) lo += step;
+    return lo;
+}
+// ... and for any number nd of draws: a scene with more than kTable of them, whose table holds nothing, is bisected in global memory
+__device__ __forceinline__ unsigned draw_of_prim(const unsigned* s_table, unsigned kTable, unsigned nd, const slhip_scene* sc,
+                                                 const slhip_draw* __restrict__ draws, unsigned prim)
+{
+    if (nd <= kTable) return table_draw_of_prim(s_table, kTable, prim);
+    unsigned lo = 0u, hi = nd;
+    while (hi - lo > 1u) {
+        const unsigned mid = (lo + hi) >> 1;
+        if (prim >= draws[sc->draw_begin + mid].prim_base) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // The shading pass's geometry resolve of one pixel against one set-up (sub-)triangle whose corners carry the barycentrics
 // q0..q2 of the ORIGINAL triangle: perspective-correct barycentrics b, facing, and -- where a texture will be sampled -- the
 // barycentrics one pixel to the right / below (the texture footprint).  Returns false if the pixel is not covered.
@@ -1905,12 +1999,7 @@ __global__ __launch_bounds__(256) SLHIP_SHADE_KERNEL void k_shade(slhip_mesh_poo
             const unsigned prim = (unsigned)(key & 0xFFFFFFFFull);
             unsigned d = sc->draw_begin;
             if (n_scene_draws <= 64) {
-                // the last draw whose first primitive id is <= prim: six halving steps over the table (padded with ~0)
-                unsigned lo = 0u;
-#pragma unroll
-                for (unsigned step = 32u; step > 0u; step >>= 1)
-                    if (prim >= s_prim_base[lo + step]) lo += step;
-                d = sc->draw_begin + lo;
+                d = sc->draw_begin + table_draw_of_prim(s_prim_base, 64u, prim);
             } else {
                 for (unsigned i = sc->draw_begin + 1; i < sc->draw_end; ++i)
                     if (prim >= draws[i].prim_base) d = i;
@@ -1943,32 +2032,12 @@ __global__ __launch_bounds__(256) SLHIP_SHADE_KERNEL void k_shade(slhip_mesh_poo
 #pragma unroll
             for (int k = 0; k < 3; ++k) pb.b[k] = pb.bx[k] = pb.by[k] = 0.0f;
             pb.front = false;
-            if (screen_all_inside(sv[0], sv[1], sv[2])) {
-                // all three corners in front of the near plane (clip_near() would hand the triangle through): set-up from the
-                // per-vertex window coordinates, no clip positions needed, the corners' barycentrics are the unit vectors
-                const float e0[3] = {1.0f, 0.0f, 0.0f}, e1[3] = {0.0f, 1.0f, 0.0f}, e2[3] = {0.0f, 0.0f, 1.0f};
-                Setup t;
-                if (setup_from_screen(sv[0], sv[1], sv[2], W, H, t)) found = resolve_pixel(t, e0, e1, e2, px, py, textured, pb);
-            } else {
-                ClipVert cv[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const float4 c4 = clipbuf[dr->clip_base + vi[k]];   // identical to what the raster used
-                    cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-                    cv[k].bary[0] = k == 0 ? 1.0f : 0.0f;
-                    cv[k].bary[1] = k == 1 ? 1.0f : 0.0f;
-                    cv[k].bary[2] = k == 2 ? 1.0f : 0.0f;
-                }
-                ClipVert poly[4];
-                const int n = clip_near(cv, poly);
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub) {   // unrolled: static indices into poly[]
-                    if (sub >= n - 2 || found) break;
-                    Setup t;
-                    if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
-                    found = resolve_pixel(t, poly[0].bary, poly[sub + 1].bary, poly[sub + 2].bary, px, py, textured, pb);
-                }
-            }
+            // (the clip positions, where the triangle needs them, are identical to what the raster used)
+            for_each_setup<true>(sv[0], sv[1], sv[2], clipbuf, dr->clip_base, vi, W, H,
+                                 [&](int, const Setup& t, const float (&q0)[3], const float (&q1)[3], const float (&q2)[3]) {
+                                     found = resolve_pixel(t, q0, q1, q2, px, py, textured, pb);
+                                     return !found;
+                                 });
             front = pb.front;
 #pragma unroll
             for (int k = 0; k < 3; ++k) { b[k] = pb.b[k]; bx[k] = pb.bx[k]; by[k] = pb.by[k]; }

@@ -85,21 +85,8 @@ __global__ __launch_bounds__(256) void k_om_visible(const slhip_scene* __restric
         const unsigned long long key = p < P ? v[p] : kVisEmpty;
         if (key != kVisEmpty && nd > 0u) {
             const unsigned prim = (unsigned)(key & 0xFFFFFFFFull);
-            unsigned slot;
-            if (lds_draws) {
-                unsigned lo = 0u;
-#pragma unroll
-                for (unsigned step = kOsLdsDraws / 2; step > 0u; step >>= 1)
-                    if (prim >= s_prim[lo + step]) lo += step;
-                slot = s_slot[lo];
-            } else {
-                unsigned lo = 0u, hi = nd;   // the last k with prim_base[k] <= prim (draw 0 starts at primitive 0)
-                while (hi - lo > 1u) {
-                    const unsigned mid = (lo + hi) >> 1;
-                    if (prim >= draws[sc->draw_begin + mid].prim_base) lo = mid; else hi = mid;
-                }
-                slot = os_slot(draws + sc->draw_begin + lo);
-            }
+            const unsigned k = draw_of_prim(s_prim, kOsLdsDraws, nd, sc, draws, prim);
+            const unsigned slot = lds_draws ? s_slot[k] : os_slot(draws + sc->draw_begin + k);
             if (slot != 0u && slot < n_slots) {
                 const OmRec* r = mrec + slot;
                 const int x = (int)(p % (size_t)W), y = (int)(p / (size_t)W);

@@ -140,40 +140,21 @@ __global__ __launch_bounds__(1024) void k_os_scan(OsRec* __restrict__ out, size_
     if (threadIdx.x == 0) *total = s_carry;
 }
 
-// fragment emission into the slot's tile words: MainTarget's depth rules and alpha test, no peel test, no key
+// fragment emission into the slot's tile words: MainTarget's depth rules and its AlphaTest, no peel test, no key
 struct StatsTarget {
     unsigned long long* words;   // the slot's run
     int tx0, ty0, tx1, ty1;      // its tile box
-    const float* bary;           // [3][3] (alpha test only)
-    const float* uv;             // [3][2]
-    const uint8_t* pool_tex;     // nullptr = no alpha test
-    unsigned tex;
-    int tex_w, tex_h;
-    unsigned tex_sampler;
-    float base_alpha, alpha_cutoff;
+    AlphaTest alpha;             // pool_tex == nullptr: no alpha test
 
     __device__ __forceinline__ bool passes(const Setup& t, int px, int py, const float* l) const
     {
         const float z = interp(l, t.z[0], t.z[1], t.z[2]);
         if (!(z >= 0.0f && z <= 1.0f)) return false;
         if (depth24(z) >= 0xFFFFFFu) return false;   // a fragment AT the far plane loses (R6)
-        if (pool_tex) {   // the discard test of MainTarget::emit, operation for operation
-            const float pw0 = l[0] * t.invw[0], pw1 = l[1] * t.invw[1], pw2 = l[2] * t.invw[2];
-            const float sw = (pw0 + pw1) + pw2;
-            const float bs[3] = {pw0 * (1.0f / sw), pw1 * (1.0f / sw), pw2 * (1.0f / sw)};
+        if (alpha.pool_tex) {
             float b[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                b[k] = fmaf(bs[2], bary[6 + k], fmaf(bs[1], bary[3 + k], bs[0] * bary[k]));
-            const float u = interp(b, uv[0], uv[2], uv[4]);
-            const float v = interp(b, uv[1], uv[3], uv[5]);
-            float bx[3], by[3];
-            bary_at(t, bary, bary + 3, bary + 6, px + 1, py, bx);
-            bary_at(t, bary, bary + 3, bary + 6, px, py + 1, by);
-            float tc[4];
-            tex_sample(pool_tex, tex, tex_w, tex_h, tex_sampler, u, v, interp(bx, uv[0], uv[2], uv[4]) - u, interp(bx, uv[1], uv[3], uv[5]) - v,
-                       interp(by, uv[0], uv[2], uv[4]) - u, interp(by, uv[1], uv[3], uv[5]) - v, tc);
-            if (base_alpha * tc[3] < alpha_cutoff) return false;
+            alpha.persp_bary(t, l, b);
+            if (alpha.discards(t, px, py, b)) return false;
         }
         return true;
     }
@@ -201,13 +182,12 @@ __device__ __forceinline__ bool os_target(const OsRec* __restrict__ out, unsigne
     tgt.tx0 = r->bbox_obj[0]; tgt.ty0 = r->bbox_obj[1]; tgt.tx1 = r->bbox_obj[2]; tgt.ty1 = r->bbox_obj[3];
     if (tgt.tx0 > tgt.tx1) return false;
     tgt.words = pool_words + *reinterpret_cast<const unsigned long long*>(r->bbox_visib);
-    tgt.pool_tex = nullptr;
+    tgt.alpha.pool_tex = nullptr;
     return true;
 }
 
-// raster_chunk() with the silhouette target: the same triangles, the same set-up paths (window coordinates of the vertex pass
-// for triangles entirely in front of the near plane, clip_near + setup_tri otherwise), the same queue for large triangles.
-// kAttr: the alpha-tested draws (per-pixel walk, as in raster_chunk<true>).
+// raster_chunk() with the silhouette target: the same triangles through the same definitions (for_each_setup, walk_attr_tri), the
+// same queue for large triangles.  kAttr: the alpha-tested draws (per-pixel walk, as in raster_chunk<true>).
 template <bool kAttr>
 __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_os_raster(slhip_mesh_pool pool, const slhip_draw* __restrict__ draws,
                                                    const slhip_chunk* __restrict__ chunks, unsigned n_chunks, int W, int H,
@@ -219,81 +199,24 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_os_raster(slhip_mesh
         const slhip_chunk ch = chunks[c];
         if (threadIdx.x >= ch.count) continue;
         const slhip_draw* dr = draws + ch.draw;
-        const bool alpha_test = (dr->flags & SLHIP_DRAW_ALPHA_TEST) && (dr->flags & SLHIP_DRAW_HAS_BASE_TEX);
-        if (alpha_test != kAttr) continue;
+        if (draw_alpha_tested(dr->flags) != kAttr) continue;
         StatsTarget tgt;
         if (!os_target(out, n_slots, ch.scene, dr, pool_words, tgt)) continue;
         const unsigned tri = ch.first_tri + threadIdx.x;
         const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
         const unsigned vi[3] = {ip[0], ip[1], ip[2]};
         if constexpr (!kAttr) {
-            tgt.bary = nullptr; tgt.uv = nullptr;
             const uint4 s0 = screen[dr->clip_base + vi[0]], s1 = screen[dr->clip_base + vi[1]], s2 = screen[dr->clip_base + vi[2]];
-            if (screen_all_inside(s0, s1, s2)) {
-                Setup t;
-                if (setup_from_screen(s0, s1, s2, W, H, t)) raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri, ch.scene, kSmallArea);
-                continue;
-            }
-            ClipVert cv[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float4 c4 = clipbuf[dr->clip_base + vi[k]];
-                cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-                cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
-            }
-            ClipVert poly[4];
-            const int n = clip_near(cv, poly);
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-                if (sub >= n - 2) break;
-                Setup t;
-                if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
+            for_each_setup<false>(s0, s1, s2, clipbuf, dr->clip_base, vi, W, H, [&](int sub, const Setup& t, const float*, const float*, const float*) {
                 raster_or_enqueue(t, tgt, queue, capacity, ch.draw, tri | ((unsigned)sub << 31), ch.scene, kSmallArea);
-            }
+                return true;
+            });
         } else {
             ClipVert cv[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float4 c4 = clipbuf[dr->clip_base + vi[k]];
-                cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-                cv[k].bary[0] = k == 0 ? 1.0f : 0.0f;
-                cv[k].bary[1] = k == 1 ? 1.0f : 0.0f;
-                cv[k].bary[2] = k == 2 ? 1.0f : 0.0f;
-            }
-            ClipVert poly[4];
-            const int n = clip_near(cv, poly);
-            if (n == 0) continue;
+            clip_tri<true>(clipbuf, dr->clip_base, vi, cv);
             float uvs[6];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float2 uv = reinterpret_cast<const float2*>(pool.d_uv)[dr->vtx_base + vi[k]];
-                uvs[2 * k] = uv.x; uvs[2 * k + 1] = uv.y;
-            }
-            tgt.pool_tex = pool.d_tex; tgt.tex = dr->tex_offset;
-            tgt.tex_w = (int)dr->tex_w; tgt.tex_h = (int)dr->tex_h;
-            tgt.tex_sampler = dr->tex_sampler[0];
-            tgt.uv = uvs;
-            tgt.base_alpha = dr->base_color[3];
-            tgt.alpha_cutoff = dr->alpha_cutoff;
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub) {
-                if (sub >= n - 2) break;
-                Setup t;
-                if (!setup_tri(poly[0].clip, poly[sub + 1].clip, poly[sub + 2].clip, W, H, t)) continue;
-                float bary[9];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    bary[k] = poly[0].bary[k];
-                    bary[3 + k] = poly[sub + 1].bary[k];
-                    bary[6 + k] = poly[sub + 2].bary[k];
-                }
-                tgt.bary = bary;
-                for (int py = t.ymin; py <= t.ymax; ++py)
-                    for (int px = t.xmin; px <= t.xmax; ++px) {
-                        float l[3];
-                        if (coverage(t, px, py, l)) tgt.emit(t, px, py, l);
-                    }
-            }
+            tgt.alpha = AlphaTest::from_draw(pool, dr, vi, uvs);
+            walk_attr_tri(cv, W, H, tgt);
         }
     }
 }
@@ -318,27 +241,8 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_os_large(slhip_mesh_
         StatsTarget tgt;
         const slhip_draw* dr = draws + en.draw;
         if (!os_target(out, n_slots, en.scene_aux, dr, pool_words, tgt)) continue;
-        const unsigned tri = en.tri_sub & 0x7FFFFFFFu;
-        const int sub = (int)(en.tri_sub >> 31);
-        const unsigned* ip = pool.d_idx + dr->idx_base + 3 * (size_t)tri;
-        const uint4 s0 = screen[dr->clip_base + ip[0]], s1 = screen[dr->clip_base + ip[1]], s2 = screen[dr->clip_base + ip[2]];
-        const bool cached = screen_all_inside(s0, s1, s2);
-        if (cached && (sub != 0 || !setup_from_screen(s0, s1, s2, W, H, t))) continue;
-        if (!cached) {
-            ClipVert cv[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float4 c4 = clipbuf[dr->clip_base + ip[k]];
-                cv[k].clip[0] = c4.x; cv[k].clip[1] = c4.y; cv[k].clip[2] = c4.z; cv[k].clip[3] = c4.w;
-                cv[k].bary[0] = cv[k].bary[1] = cv[k].bary[2] = 0.0f;
-            }
-            ClipVert poly[4];
-            const int n = clip_near(cv, poly);
-            if (sub > n - 3) continue;
-            const ClipVert& pb = sub == 0 ? poly[1] : poly[2];
-            const ClipVert& pc = sub == 0 ? poly[2] : poly[3];
-            if (!setup_tri(poly[0].clip, pb.clip, pc.clip, W, H, t)) continue;
-        }
+        unsigned tri;
+        if (!entry_setup(en, dr, pool, screen, clipbuf, W, H, t, tri)) continue;
         TilePixels tp(en, k0, lane);
         for (unsigned k = k0; k < k1; ++k) {
             int px, py;
@@ -428,7 +332,7 @@ __device__ __forceinline__ void os_flush(OsRec* __restrict__ grec, int* __restri
 }
 
 // grid (blocks per scene, scene): one pass over the visibility keys.  A pixel's key -> primitive -> draw (the last of the scene's
-// draws whose first primitive id is <= the primitive: k_shade's rule) -> slot.  Each thread walks pixels 256 apart and keeps a
+// draws whose first primitive id is <= the primitive: draw_of_prim) -> slot.  Each thread walks pixels 256 apart and keeps a
 // run of one slot in registers (pixels of slot 0 do not break it); a run goes to LDS (or to the record) when the slot changes.
 __global__ __launch_bounds__(256) void k_os_visible(const slhip_scene* __restrict__ scenes, const slhip_draw* __restrict__ draws,
                                                     const unsigned long long* __restrict__ vis, int W, int H, unsigned n_slots,
@@ -460,21 +364,8 @@ __global__ __launch_bounds__(256) void k_os_visible(const slhip_scene* __restric
         const unsigned long long key = v[p];
         if (key == kVisEmpty) continue;
         const unsigned prim = (unsigned)(key & 0xFFFFFFFFull);
-        unsigned slot;
-        if (lds_draws) {
-            unsigned lo = 0u;
-#pragma unroll
-            for (unsigned step = kOsLdsDraws / 2; step > 0u; step >>= 1)
-                if (prim >= s_prim[lo + step]) lo += step;
-            slot = s_slot[lo];
-        } else {
-            unsigned lo = 0u, hi = nd;   // the last k with prim_base[k] <= prim (draw 0 starts at primitive 0)
-            while (hi - lo > 1u) {
-                const unsigned mid = (lo + hi) >> 1;
-                if (prim >= draws[sc->draw_begin + mid].prim_base) lo = mid; else hi = mid;
-            }
-            slot = os_slot(draws + sc->draw_begin + lo);
-        }
+        const unsigned k = draw_of_prim(s_prim, kOsLdsDraws, nd, sc, draws, prim);
+        const unsigned slot = lds_draws ? s_slot[k] : os_slot(draws + sc->draw_begin + k);
         if (slot == 0u || slot >= n_slots) continue;
         if (slot != cur) {
             if (cnt > 0) os_flush(grec, s_acc, cur, cnt, xmn, ymn, xmx, ymx);

@@ -229,6 +229,44 @@ def test_alpha_tested_draw(sl, eng):
     assert pa[1] > 0 and pa[1] < bo[1][2] * bo[1][3]
 
 
+def test_alpha_tested_draw_across_the_near_plane(sl, eng, oracle):
+    # The one case in which the clipped sub-triangles, their barycentrics and the discard test meet, in the visibility pass, the
+    # shading pass and the silhouette pass.  Object 1 faces the camera 0.1 m away, turned 0.03 rad about two axes: its plane cuts
+    # the near plane (z = 0.1) along a slanted line through the picture, almost parallel to it, so some pixel centre next to
+    # the cut has a camera z within 1e-6 of 0.1.  Object 2 stands 0.45 m from the camera and shows through the holes.
+    mesh = sl.Mesh.from_data(holey_quad(2))
+    scene = sl.Scene((64, 48), seed=1)
+    upright = np.array([[1, 0, 0], [0, 0, -1], [0, 1, 0]], np.float64)   # the quad's normal along -y, towards the camera
+    c, s = np.cos(0.03), np.sin(0.03)
+    turn = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]]) @ np.array([[1, 0, 0], [0, c, -s], [0, s, c]])
+    for rot, xyz in ((turn @ upright, (0.0, 0.0, 0.5)), (upright, (0.02, 0.35, 0.52))):
+        o = sl.Object(mesh)
+        p = np.eye(4, dtype=np.float32)
+        p[:3, :3] = rot.astype(np.float32)
+        p[:3, 3] = xyz
+        o.set_pose(torch.from_numpy(p))
+        scene.add_object(o)
+    scene.set_camera_look_at(torch.tensor([0.0, -0.1, 0.5]), torch.tensor([0.0, 1.0, 0.5]))
+    scene.background_plane_size = torch.tensor([2.0, 2.0])
+    pool = HostPool()
+    srec, drec, _ = build_batch([scene], pool)
+    assert (drec["flags"][1:] & _abi.DRAW_ALPHA_TEST).all()
+    bufs = render_stats(eng, [scene])
+    st = bufs.object_stats
+    check_visible(bufs, 3)
+    check_silhouette(eng, scene, st)
+    check_invariants(st)
+    ref = oracle.render(pool.arrays(), srec, drec, 64, 48, _abi.OUT_INSTANCE | _abi.OUT_COORD)
+    inst = bufs.instance.cpu().numpy().view(np.uint16)
+    coord = bufs.coord.cpu().numpy()
+    assert np.array_equal(inst, ref.instance) and np.array_equal(coord.view(np.uint32), ref.coord.view(np.uint32))
+    near = coord[0, :, :, 3][inst[0, ..., 0] == 1]
+    assert abs(float(near.min()) - 0.1) < 1e-6          # cut exactly at the near plane, inside the picture
+    pv, pa, _, bo = np_stats(st, 0)
+    assert 0 < pa[1] < bo[1][2] * bo[1][3]              # the holes show
+    assert 0 < pv[2] < pa[2]                            # ... and object 2 through them, partly
+
+
 def test_silhouette_matches_the_oracle(sl, eng, oracle):
     scene = S.clutter_scene(sl, 13, n_objects=6)
     W, H = scene.viewport

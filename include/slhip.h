@@ -1158,6 +1158,114 @@ int slhip_pose_error_host(const slhip_pose_error_params* params, const slhip_pos
 int slhip_pose_error_timing_enable(int on);
 int slhip_pose_error_timings(float ms_out[2]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pose VSD: BOP's Visible Surface Discrepancy of pose estimates against a batch's ground truth, the
+ * one pose error that looks at the picture.  The object is drawn as depth at the ground truth and at
+ * the estimate, both are compared where either is visible in the scene's depth image.  This project's
+ * addition, the reference has no counterpart.  All float32, one rounded IEEE operation at a time (no
+ * fma), the coverage in exact integers; csrc/slhip_vsd_rules.h holds the rules for host and device,
+ * tests/pose_vsd_ref.py restates them in NumPy bit for bit.  DESIGN.md "Pose VSD".
+ *
+ * The surface bank: vertices (x, y, z, 1) in the object frame and triangles of absolute vertex indices;
+ * class a owns triangles [tri_begin[a], tri_begin[a] + tri_count[a]).  A class with tri_count 0 or a range
+ * that leaves the table, and a class index outside the bank, has no surface: vsd = +inf, counts -1.  A
+ * triangle with an index >= n_vertices is dropped.
+ *
+ * Rasterising a pose M (3 x 4 row-major, object to camera, +Z forward) of a class, per triangle:
+ *   (X, Y, Z) = M p per vertex, rows ((m0*x + m1*y) + m2*z) + m3.  A vertex with a non-finite X, Y or Z or
+ *   without Z > z_near is clipped: its triangles are dropped and the hypothesis gets SLHIP_VSD_CLIPPED (a
+ *   triangle of the ground truth's pose: every hypothesis of the object).  There is no clip-space path.
+ *   u = (fx * X) / Z + cx,  v = (fy * Y) / Z + cy,  Xs = (int)clamp(floorf(u * 256.0f + 0.5f), -2^26, 2^26)
+ *   (a NaN gives 0), Ys likewise of v; the centre of pixel (px, py) is (256 px + 128, 256 py + 128).
+ *   area2 = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0); 0: dropped; flipped = area2 < 0, area2 = |area2|.
+ *   e_i = slhip_raster::edge_value(i) at the centre; covered when e_0, e_1, e_2 >= 0 (no ownership bias, no
+ *   culling).  b_i = (float)e_i / (float)area2, iz_k = 1.0f / Z_k,
+ *   z = 1.0f / ((b_0 * iz_0 + b_1 * iz_1) + b_2 * iz_2); the pose's depth is the minimum over its triangles.
+ * Comparing, per pixel, with z_g, z_e the two depths (present_g, present_e: covered at all) and t the scene's
+ * depth at d_test_depth[((scene * H + py) * W + px) * depth_stride]:
+ *   absent_t = !(t > 0) || t - t != 0
+ *   xn = (((float)px + 0.5f) - cx) / fx, yn likewise, ray = sqrtf((xn*xn + yn*yn) + 1.0f)
+ *   D_g = z_g * ray, D_e = z_e * ray, D_t = t * ray
+ *   vis(m) = present_m && (absent_t || (D_m - D_t) <= delta)
+ *   V_g = vis(g), V_e = vis(e) || (V_g && present_e), inter = V_g && V_e, uni = V_g || V_e
+ *   cost_t = inter && fabsf(D_g - D_e) >= thr_t,  thr_t = taus[t], or taus[t] * diameter[class] with
+ *   SLHIP_VSD_NORMALIZED
+ * and over the picture the int32 counts n_visib_gt, n_visib_est, n_inter, n_union, n_cost[t]:
+ *   vsd[t] = n_union == 0 ? 1.0f : (float)(n_cost[t] + (n_union - n_inter)) / (float)n_union
+ * A pose (ground truth or estimate) with an entry that is not finite: vsd NaN, counts and n_cost -1, flags 0.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_VSD_TAUS_MAX   16
+#define SLHIP_VSD_WIDTH_MAX  4096u    /* a row of the picture must fit the smallest LDS band             */
+#define SLHIP_VSD_NORMALIZED 1u       /* params.flags: thresholds are taus[t] * diameter[class]          */
+#define SLHIP_VSD_CLIPPED    1u       /* output flags: a triangle had a vertex at or behind z_near       */
+#define SLHIP_VSD_OUT_VSD    1u
+#define SLHIP_VSD_OUT_COUNTS 2u
+#define SLHIP_VSD_OUT_COST   4u
+#define SLHIP_VSD_OUT_FLAGS  8u
+
+typedef struct {
+    float fx, fy, cx, cy;      /* fx, fy > 0, all finite                                                      */
+    int32_t W, H;              /* the picture: W 1..SLHIP_VSD_WIDTH_MAX, H 1..32768                           */
+    uint32_t n_objects;        /* O, 1..SLHIP_SYNTH_MAX_OBJECTS                                               */
+    uint32_t n_hypotheses;     /* Hy >= 1                                                                     */
+    uint32_t n_taus;           /* T, 1..SLHIP_VSD_TAUS_MAX                                                    */
+    float delta;               /* tolerance of the visibility test, >= 0 and finite                           */
+    float z_near;              /* > 0 and finite                                                              */
+    uint32_t flags;            /* SLHIP_VSD_NORMALIZED or 0                                                   */
+    uint32_t outputs;          /* SLHIP_VSD_OUT_* bits, at least one (slhip_pose_depth does not read them)    */
+    uint32_t _pad[3];
+    float taus[SLHIP_VSD_TAUS_MAX];   /* the first n_taus finite and >= 0                                     */
+} slhip_pose_vsd_params; /* 128 bytes */
+
+typedef struct {
+    const float* vertices;     /* f32 [n_vertices, 4], 16-byte aligned                                        */
+    const uint32_t* triangles; /* u32 [n_triangles, 3]                                                        */
+    const uint32_t* tri_begin; /* u32 [n_assets]                                                              */
+    const uint32_t* tri_count; /* u32 [n_assets]                                                              */
+    const float* diameter;     /* f32 [n_assets]; required with SLHIP_VSD_NORMALIZED, else may be NULL        */
+    uint32_t n_assets;         /* 1..SLHIP_SYNTH_MAX_ASSETS                                                   */
+    uint32_t n_vertices;       /* 1..2^31 - 1                                                                 */
+    uint32_t n_triangles;      /* 1..2^31 - 1                                                                 */
+    uint32_t _pad;
+} slhip_pose_surface; /* 56 bytes; the arrays on the device, or on the host for the _host entries */
+
+typedef struct {               /* read only when its bit is set                                               */
+    float* vsd;                /* f32 [n_scenes, O, Hy, T]                                                    */
+    int32_t* counts;           /* i32 [n_scenes, O, Hy, 4]: visib_gt, visib_est, inter, union                 */
+    int32_t* n_cost;           /* i32 [n_scenes, O, Hy, T]                                                    */
+    uint32_t* flags;           /* u32 [n_scenes, O, Hy]                                                       */
+} slhip_pose_vsd_out;
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_pose_vsd_check_params(const slhip_pose_vsd_params* params);
+/* d_classes i32, read at (scene * O + object) * class_stride (1: a plain tensor, 4: slhip_synth_object records in place);
+ * d_gt f32 [n_scenes, O, 3, 4]; d_est f32 [n_scenes, O, Hy, 3, 4]; d_test_depth read with depth_stride floats between
+ * pixels (4 on the w of d_coord, 1 on a dense plane).  Every output named in params->outputs is written exactly once per
+ * hypothesis, the others are not touched.  n_scenes == 0 does nothing; null pointers, misalignment, class_stride or
+ * depth_stride 0 and bad parameters are refused before anything touches the device.  One workgroup per (scene, object,
+ * hypothesis); the two depth planes live in LDS only.  Asynchronous on `stream`.                                          */
+int slhip_pose_vsd(const slhip_pose_vsd_params* params, const slhip_pose_surface* surface, const int32_t* d_classes,
+                   uint32_t class_stride, const float* d_gt, const float* d_est, const float* d_test_depth,
+                   uint32_t depth_stride, uint32_t n_scenes, const slhip_pose_vsd_out* out, void* stream);
+/* The raster alone: d_poses f32 [n_scenes, O, Hy, 3, 4] drawn into d_depth f32 [n_scenes, O, Hy, H, W], 0 where nothing is
+ * covered (and everywhere for a class without a surface or a pose that is not finite); d_flags u32 [n_scenes, O, Hy] or
+ * NULL.  Every float of d_depth is written exactly once.  The whole record must pass slhip_pose_vsd_check_params, though
+ * outputs, n_taus, taus, delta and flags do not enter the raster.                                                         */
+int slhip_pose_depth(const slhip_pose_vsd_params* params, const slhip_pose_surface* surface, const int32_t* d_classes,
+                     uint32_t class_stride, const float* d_poses, uint32_t n_scenes, float* d_depth, uint32_t* d_flags,
+                     void* stream);
+/* The same rules on host arrays through csrc/slhip_vsd_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_pose_vsd_host(const slhip_pose_vsd_params* params, const slhip_pose_surface* h_surface, const int32_t* h_classes,
+                        uint32_t class_stride, const float* h_gt, const float* h_est, const float* h_test_depth,
+                        uint32_t depth_stride, uint32_t n_scenes, const slhip_pose_vsd_out* out);
+int slhip_pose_depth_host(const slhip_pose_vsd_params* params, const slhip_pose_surface* h_surface, const int32_t* h_classes,
+                          uint32_t class_stride, const float* h_poses, uint32_t n_scenes, float* h_depth, uint32_t* h_flags);
+/* The pixels one LDS band of k_pose_vsd holds (two uint32 planes of that size).  No device. */
+int slhip_pose_vsd_band_pixels(void);
+/* Developer hook (tools/time_pose_vsd.py): HIP events round the last slhip_pose_vsd [0] and slhip_pose_depth [1]. */
+int slhip_pose_vsd_timing_enable(int on);
+int slhip_pose_vsd_timings(float ms_out[2]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).

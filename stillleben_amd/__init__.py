@@ -36,6 +36,8 @@ from . import object_regions  # noqa: F401  (additive: surface-region banks, per
 from .object_regions import RegionBank, ObjectRegions  # noqa: F401
 from . import pose_error  # noqa: F401  (additive: ADD, ADD-S, MSSD, MSPD against a batch's ground truth, with class symmetries)
 from .pose_error import ModelBank, PoseErrors  # noqa: F401
+from . import pose_vsd  # noqa: F401  (additive: BOP's VSD against a batch's ground truth, by a depth raster in LDS)
+from .pose_vsd import PoseVSD, SurfaceBank  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -45,6 +47,7 @@ __all__ = [
     'bop', 'depth_sensor', 'object_crops', 'ObjectCrops', 'object_points', 'ObjectPoints',
     'object_keypoints', 'KeypointBank', 'ObjectKeypoints', 'object_regions', 'RegionBank', 'ObjectRegions',
     'pose_error', 'ModelBank', 'PoseErrors',
+    'pose_vsd', 'SurfaceBank', 'PoseVSD',
 ]
 
 

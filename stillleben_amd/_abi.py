@@ -52,6 +52,9 @@ KEYPOINT_IN_FRONT, KEYPOINT_INSIDE, KEYPOINT_UNOCCLUDED = 1, 2, 4      # SLHIP_K
 KEYPOINT_FIELD_OFFSET, KEYPOINT_FIELD_UNIT = 0, 1                      # SLHIP_KEYPOINT_FIELD_*
 POSE_POINTS_MAX, POSE_SYMMETRIES_MAX = 4096, 1024                      # SLHIP_POSE_POINTS_MAX, SLHIP_POSE_SYMMETRIES_MAX
 POSE_OUT_ADD, POSE_OUT_ADDS, POSE_OUT_MSSD, POSE_OUT_MSPD = 1, 2, 4, 8      # SLHIP_POSE_OUT_*
+VSD_TAUS_MAX, VSD_WIDTH_MAX = 16, 4096                                    # SLHIP_VSD_TAUS_MAX, SLHIP_VSD_WIDTH_MAX
+VSD_NORMALIZED, VSD_CLIPPED = 1, 1                                        # SLHIP_VSD_NORMALIZED (params.flags), SLHIP_VSD_CLIPPED (output flags)
+VSD_OUT_VSD, VSD_OUT_COUNTS, VSD_OUT_COST, VSD_OUT_FLAGS = 1, 2, 4, 8     # SLHIP_VSD_OUT_*
 REGIONS_MAX, REGION_NONE = 255, 255                                    # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
 REGIONS_OUT_LOCAL, REGIONS_OUT_HISTOGRAM = 1, 2                        # SLHIP_REGIONS_OUT_*
 ABI_VERSION = 5
@@ -306,6 +309,32 @@ class PoseErrorOut(C.Structure):
                 ("mspd_sym", C.c_void_p)]
 
 
+# slhip_pose_vsd_params (include/slhip.h), 128 bytes
+POSE_VSD_PARAMS_DTYPE = np.dtype([
+    ("fx", np.float32), ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("W", np.int32), ("H", np.int32),
+    ("n_objects", np.uint32), ("n_hypotheses", np.uint32), ("n_taus", np.uint32), ("delta", np.float32), ("z_near", np.float32),
+    ("flags", np.uint32), ("outputs", np.uint32), ("_pad", np.uint32, (3,)), ("taus", np.float32, (VSD_TAUS_MAX,)),
+])
+assert POSE_VSD_PARAMS_DTYPE.itemsize == 128
+
+
+class PoseSurface(C.Structure):
+    """slhip_pose_surface: the arrays of a surface bank (device pointers, or host pointers for the _host entries)."""
+
+    _fields_ = [("vertices", C.c_void_p), ("triangles", C.c_void_p), ("tri_begin", C.c_void_p), ("tri_count", C.c_void_p),
+                ("diameter", C.c_void_p), ("n_assets", C.c_uint32), ("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+assert C.sizeof(PoseSurface) == 56
+
+
+class PoseVsdOut(C.Structure):
+    """slhip_pose_vsd_out: the output pointers of slhip_pose_vsd."""
+
+    _fields_ = [("vsd", C.c_void_p), ("counts", C.c_void_p), ("n_cost", C.c_void_p), ("flags", C.c_void_p)]
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -530,6 +559,19 @@ def lib():
                                             C.c_uint32, C.POINTER(PoseErrorOut)]
         L.slhip_pose_error_timing_enable.argtypes = [C.c_int]
         L.slhip_pose_error_timings.argtypes = [C.POINTER(C.c_float * 2)]
+    if hasattr(L, "slhip_pose_vsd"):                 # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_pose_vsd_check_params.argtypes = [C.c_void_p]
+        L.slhip_pose_vsd.argtypes = [C.c_void_p, C.POINTER(PoseSurface), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint32, C.c_uint32, C.POINTER(PoseVsdOut), C.c_void_p]
+        L.slhip_pose_vsd_host.argtypes = [C.c_void_p, C.POINTER(PoseSurface), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PoseVsdOut)]
+        L.slhip_pose_depth.argtypes = [C.c_void_p, C.POINTER(PoseSurface), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
+        L.slhip_pose_depth_host.argtypes = [C.c_void_p, C.POINTER(PoseSurface), C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                            C.c_void_p, C.c_void_p]
+        L.slhip_pose_vsd_band_pixels.argtypes = []
+        L.slhip_pose_vsd_timing_enable.argtypes = [C.c_int]
+        L.slhip_pose_vsd_timings.argtypes = [C.POINTER(C.c_float * 2)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

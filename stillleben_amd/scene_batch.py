@@ -539,6 +539,30 @@ class SceneBatch:
         return pose_error.evaluate(self.object_to_camera[s0:s0 + B], estimates, self.d_objects[s0 * nb:(s0 + B) * nb], bank,
                                    self.intrinsics(), **kw)
 
+    def pose_vsd(self, estimates, surface, buffers, chunk=None, **kw):
+        """sl.pose_vsd.evaluate of pose estimates against the batch's own ground truth: its `object_to_camera`, its object records
+        (read in place), its intrinsics, and the scene's depth from the w of `buffers.coord` (`buffers` = what render(chunk, ...)
+        returned).  `estimates`: float32 [B, O, Hy, 3, 4] or [B, O, 3, 4] for the scenes of render chunk `chunk`; None: the
+        buffers hold every scene of the batch.  `surface`: a SurfaceBank of the batch's table (sl.pose_vsd.surface(table)).
+        `kw`: taus, delta, normalized, z_near, outputs.  Needs place(object_to_camera=True) for the view last placed."""
+        from . import pose_vsd
+
+        for name in ("intrinsics", "object_to_camera", "objects", "depth"):
+            if name in kw:
+                raise TypeError("SceneBatch.pose_vsd sets `%s` itself" % name)
+        if self.object_to_camera is None or not self._object_to_camera_placed:
+            raise RuntimeError("SceneBatch.pose_vsd needs object_to_camera of the view last placed: call "
+                               "place(object_to_camera=True) (the last place() did not keep it)")
+        if buffers.coord is None:
+            raise RuntimeError("pose_vsd: the `coord` target was not rendered, and the scene's depth is its w")
+        held = int(buffers.coord.shape[0])
+        s0, B = (0, self.n_scenes) if chunk is None else self._chunk_range(chunk, held)
+        if held < B:
+            raise ValueError("pose_vsd: the buffers hold %d scenes, the estimates are for %d" % (held, B))
+        nb = self.n_objects * _abi.SYNTH_OBJECT_DTYPE.itemsize
+        return pose_vsd.evaluate(self.object_to_camera[s0:s0 + B], estimates, self.d_objects[s0 * nb:(s0 + B) * nb], surface,
+                                 buffers.coord[:B], self.intrinsics(), **kw)
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

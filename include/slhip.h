@@ -1266,6 +1266,98 @@ int slhip_pose_vsd_band_pixels(void);
 int slhip_pose_vsd_timing_enable(int on);
 int slhip_pose_vsd_timings(float ms_out[2]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pose PnP: the pose of every set of K 2D-3D correspondences (a pixel position and a point in the
+ * object frame) by P3P inside RANSAC and Gauss-Newton on the inliers -- the step between the
+ * correspondence targets (`coord`, slhip_object_points_gather) and the pose errors above.  This
+ * project's addition, the reference has no counterpart.  All float32, one rounded IEEE operation at a
+ * time (no fma), only + - * / sqrt fabs min max and comparisons; csrc/slhip_pnp_rules.h holds the rules
+ * for host and device, so slhip_pose_pnp_host gives the device's outputs bit for bit.  DESIGN.md
+ * "Pose PnP" states them operation by operation; in short, per set:
+ *   1. valid list: correspondence j counts when u, v, x, y, z are finite and w > 0; the valid ones are
+ *      taken in ascending j, n_valid of them; fewer than 4: SLHIP_PNP_INSUFFICIENT.  The centre of pixel
+ *      (x, y) is (x + 0.5, y + 0.5); bearings are a = (u - cx) / fx, b = (v - cy) / fy.
+ *   2. hypothesis h draws Philox counter (set_id_base + set, 7, h, 0x51DE5EED) under (seed_lo, seed_hi)
+ *      ("Randomness" below); word k picks min(n_valid - 1, (uint32_t)(uniform(x_k) * (float)n_valid)) of
+ *      the valid list; the first three are the sample, the fourth disambiguates; a repeated pick: void.
+ *   3. P3P on the three bearings and points (a quartic free of cosines, its roots by sign changes and a
+ *      fixed number of halvings, three Newton steps on the distances); a solution is kept when every
+ *      entry is finite, the three distances are > 0 and the squared sides are met within 2^-10 of
+ *      themselves; of the kept the smallest squared pixel error of the fourth point wins (one not in
+ *      front counts +inf), ties to the lower root; none kept: void.
+ *   4. score = the number of valid correspondences with Z > 0 and ((fx*X)/Z + cx - u)^2 +
+ *      ((fy*Y)/Z + cy - v)^2 <= threshold_px^2, (X, Y, Z) the rows ((m0*x + m1*y) + m2*z) + m3; a void
+ *      hypothesis scores 0.  The winner: highest score, ties to the lowest index, d_init as index -1.
+ *      A winner below min_inliers: SLHIP_PNP_NO_MODEL.
+ *   5. refine_iters Gauss-Newton steps on the pixel residuals of the inliers of the current pose,
+ *      (omega, t) applied on the left through the Cayley map of omega / 2; the 27 sums in the order of the
+ *      pose errors' means (lane l of 256 over valid points l, l + 256, ..; the butterfly; ((w0 + w1) + w2)
+ *      + w3); L D L^T without pivoting; a pivot not positive and finite: SLHIP_PNP_REFINE_STOPPED, the
+ *      pose of the step before stays.
+ *   6. inliers, count and rms = sqrt(sum of squared errors / (float)count) of the refined pose over the
+ *      correspondences j in their own order (lane j % 256); fewer inliers than the winner's score: the
+ *      winner's pose and figures with SLHIP_PNP_REFINE_REJECTED.
+ * INSUFFICIENT and NO_MODEL give a NaN pose, 0 inliers, NaN rms, best -2 and zero bits -- never an
+ * identity pose, which would read as an answer.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_PNP_POINTS_MAX      4096u
+#define SLHIP_PNP_HYPOTHESES_MAX  4096u
+#define SLHIP_PNP_REFINE_MAX      16u
+#define SLHIP_PNP_OUT_POSE      1u
+#define SLHIP_PNP_OUT_N_INLIERS 2u
+#define SLHIP_PNP_OUT_RMS       4u
+#define SLHIP_PNP_OUT_INLIERS   8u
+#define SLHIP_PNP_OUT_BEST      16u
+#define SLHIP_PNP_OUT_FLAGS     32u
+#define SLHIP_PNP_INSUFFICIENT    1      /* flags: fewer than 4 valid correspondences                          */
+#define SLHIP_PNP_NO_MODEL        2      /* flags: no hypothesis reached min_inliers                           */
+#define SLHIP_PNP_REFINE_STOPPED  4      /* flags: a pivot of the normal equations was not positive and finite */
+#define SLHIP_PNP_REFINE_REJECTED 8      /* flags: the refined pose held fewer inliers; the winner is returned */
+
+typedef struct {
+    float fx, fy, cx, cy;      /* intrinsics of every set without a row in d_intrinsics; fx, fy > 0, all finite */
+    uint32_t n_sets;           /* M                                                                           */
+    uint32_t n_points;         /* K, 4..SLHIP_PNP_POINTS_MAX                                                  */
+    uint32_t n_hypotheses;     /* Hy, 0..SLHIP_PNP_HYPOTHESES_MAX; 0 needs d_init (a pure refinement)         */
+    float threshold_px;        /* inlier threshold in pixels, > 0 and finite                                  */
+    uint32_t refine_iters;     /* 0..SLHIP_PNP_REFINE_MAX                                                     */
+    uint32_t min_inliers;      /* >= 4                                                                        */
+    uint32_t seed_lo, seed_hi; /* Philox key                                                                  */
+    uint32_t set_id_base;      /* set i draws as set_id_base + i                                              */
+    uint32_t outputs;          /* SLHIP_PNP_OUT_* bits, at least one                                          */
+    uint32_t _pad[2];
+} slhip_pose_pnp_params; /* 64 bytes */
+
+typedef struct {               /* read only when its bit is set                                               */
+    float* pose;               /* f32 [M, 3, 4], object to camera                                             */
+    int32_t* n_inliers;        /* i32 [M]                                                                     */
+    float* rms;                /* f32 [M], reprojection RMS of the inliers in pixels                          */
+    uint32_t* inliers;         /* u32 [M, ceil(K / 32)], bit j & 31 of word j >> 5                            */
+    int32_t* best;             /* i32 [M], the winning hypothesis; -1: d_init; -2: none                       */
+    int32_t* flags;            /* i32 [M], SLHIP_PNP_* flag bits                                              */
+} slhip_pose_pnp_out;
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_pose_pnp_check_params(const slhip_pose_pnp_params* params);
+/* d_uv f32 [M, K, 2] (8-byte aligned); d_xyz f32 [M, K, 4]: the object-frame point and a weight word (16-byte aligned;
+ * slhip_object_points_gather's d_coord works as it is, its w is the camera depth); d_intrinsics NULL or f32 [M, 4] (fx, fy, cx,
+ * cy) per set, 16-byte aligned (a crop has its own); d_init NULL or f32 [M, 3, 4], a pose that competes as index -1 and wins
+ * ties.  Every output named in params->outputs is written exactly once per set, the others are not touched.  n_sets == 0 does
+ * nothing; null pointers (an output named in the mask included), misalignment, Hy == 0 without d_init and bad parameters are
+ * refused before anything touches the device.  One workgroup per set.  Asynchronous on `stream`.                          */
+int slhip_pose_pnp(const slhip_pose_pnp_params* params, const float* d_uv, const float* d_xyz, const float* d_intrinsics,
+                   const float* d_init, const slhip_pose_pnp_out* out, void* stream);
+/* The same rules on host arrays through csrc/slhip_pnp_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_pose_pnp_host(const slhip_pose_pnp_params* params, const float* h_uv, const float* h_xyz, const float* h_intrinsics,
+                        const float* h_init, const slhip_pose_pnp_out* out);
+/* The minimal solver alone: uv f32 [3, 2], xyz f32 [3, 3], intrinsics f32 [4], poses_out f32 [4, 3, 4].  Returns the number of
+ * solutions kept (0..4), written to the front of poses_out, or a negative error.  Host only, no device.                  */
+int slhip_pose_pnp_p3p_host(const float* uv, const float* xyz, const float* intrinsics, float* poses_out);
+/* Developer hook (tools/time_pose_pnp.py): HIP events round the last slhip_pose_pnp [0] and the last one that sampled
+ * hypotheses, n_hypotheses > 0 [1] (-1: not run).                                                                        */
+int slhip_pose_pnp_timing_enable(int on);
+int slhip_pose_pnp_timings(float ms_out[2]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).
@@ -1321,6 +1413,9 @@ int slhip_stream_destroy(void* stream);
  * x[0] scales the window, x[1] and x[2] shift it along x and y.
  * Stream 6, point ranks (slhip_object_points_gather only; its key and scene id base are the caller's): index =
  * (slot << 12) | (j >> 2), x[j & 3] places point j inside its stratum of the visible pixels ("Object points" above).
+ * Stream 7, correspondence samples (slhip_pose_pnp only; its key and set id base are the caller's, the set id stands where
+ * the scene id does): index = the hypothesis h, x[0], x[1], x[2] pick the three correspondences of the minimal sample, x[3]
+ * the fourth that disambiguates, each by the pick rule above over the n_valid correspondences ("Pose PnP" above).
  * Views (slhip_synth_place_view): azimuth and elevation of view v >= 1 are the draw of view 0 -- stream 0, index 0, words 1 and
  * 2, the same scene id, the same formulas -- under the key (seed_lo + v * 0x9E3779B9, seed_hi + v * 0xBB67AE85), each sum
  * wrapping at 32 bits.  No other draw uses the view's key: the light's normals, the environment's gates and picks and everything

@@ -38,6 +38,8 @@ from . import pose_error  # noqa: F401  (additive: ADD, ADD-S, MSSD, MSPD agains
 from .pose_error import ModelBank, PoseErrors  # noqa: F401
 from . import pose_vsd  # noqa: F401  (additive: BOP's VSD against a batch's ground truth, by a depth raster in LDS)
 from .pose_vsd import PoseVSD, SurfaceBank  # noqa: F401
+from . import pose_pnp  # noqa: F401  (additive: the pose of every set of 2D-3D correspondences by P3P RANSAC and refinement)
+from .pose_pnp import PosePnP  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -48,6 +50,7 @@ __all__ = [
     'object_keypoints', 'KeypointBank', 'ObjectKeypoints', 'object_regions', 'RegionBank', 'ObjectRegions',
     'pose_error', 'ModelBank', 'PoseErrors',
     'pose_vsd', 'SurfaceBank', 'PoseVSD',
+    'pose_pnp', 'PosePnP',
 ]
 
 

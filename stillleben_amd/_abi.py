@@ -55,6 +55,9 @@ POSE_OUT_ADD, POSE_OUT_ADDS, POSE_OUT_MSSD, POSE_OUT_MSPD = 1, 2, 4, 8      # SL
 VSD_TAUS_MAX, VSD_WIDTH_MAX = 16, 4096                                    # SLHIP_VSD_TAUS_MAX, SLHIP_VSD_WIDTH_MAX
 VSD_NORMALIZED, VSD_CLIPPED = 1, 1                                        # SLHIP_VSD_NORMALIZED (params.flags), SLHIP_VSD_CLIPPED (output flags)
 VSD_OUT_VSD, VSD_OUT_COUNTS, VSD_OUT_COST, VSD_OUT_FLAGS = 1, 2, 4, 8     # SLHIP_VSD_OUT_*
+PNP_POINTS_MAX, PNP_HYPOTHESES_MAX, PNP_REFINE_MAX = 4096, 4096, 16          # SLHIP_PNP_*_MAX
+PNP_OUT_POSE, PNP_OUT_N_INLIERS, PNP_OUT_RMS, PNP_OUT_INLIERS, PNP_OUT_BEST, PNP_OUT_FLAGS = 1, 2, 4, 8, 16, 32      # SLHIP_PNP_OUT_*
+PNP_INSUFFICIENT, PNP_NO_MODEL, PNP_REFINE_STOPPED, PNP_REFINE_REJECTED = 1, 2, 4, 8      # SLHIP_PNP_*: the flag bits of a set
 REGIONS_MAX, REGION_NONE = 255, 255                                    # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
 REGIONS_OUT_LOCAL, REGIONS_OUT_HISTOGRAM = 1, 2                        # SLHIP_REGIONS_OUT_*
 ABI_VERSION = 5
@@ -335,6 +338,22 @@ class PoseVsdOut(C.Structure):
     _fields_ = [("vsd", C.c_void_p), ("counts", C.c_void_p), ("n_cost", C.c_void_p), ("flags", C.c_void_p)]
 
 
+# slhip_pose_pnp_params (include/slhip.h), 64 bytes
+POSE_PNP_PARAMS_DTYPE = np.dtype([
+    ("fx", np.float32), ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("n_sets", np.uint32), ("n_points", np.uint32),
+    ("n_hypotheses", np.uint32), ("threshold_px", np.float32), ("refine_iters", np.uint32), ("min_inliers", np.uint32),
+    ("seed_lo", np.uint32), ("seed_hi", np.uint32), ("set_id_base", np.uint32), ("outputs", np.uint32), ("_pad", np.uint32, (2,)),
+])
+assert POSE_PNP_PARAMS_DTYPE.itemsize == 64
+
+
+class PosePnpOut(C.Structure):
+    """slhip_pose_pnp_out: the output pointers of slhip_pose_pnp."""
+
+    _fields_ = [("pose", C.c_void_p), ("n_inliers", C.c_void_p), ("rms", C.c_void_p), ("inliers", C.c_void_p), ("best", C.c_void_p),
+                ("flags", C.c_void_p)]
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -404,6 +423,7 @@ def view_key(seed_lo, seed_hi, view):
 SYNTH_STREAM_ENV = 4     # Philox stream of the environment draws (include/slhip.h, "Randomness")
 SYNTH_STREAM_CROP = 5    # Philox stream of the crop jitter (slhip_object_crops_select)
 SYNTH_STREAM_POINTS = 6  # Philox stream of the point ranks (slhip_object_points_gather)
+SYNTH_STREAM_PNP = 7     # Philox stream of the correspondence samples (slhip_pose_pnp)
 SYNTH_SAMPLE_DISTINCT = 1
 SYNTH_RANDOM_PBR = 2
 SYNTH_SHADOWS = 4
@@ -572,6 +592,13 @@ def lib():
         L.slhip_pose_vsd_band_pixels.argtypes = []
         L.slhip_pose_vsd_timing_enable.argtypes = [C.c_int]
         L.slhip_pose_vsd_timings.argtypes = [C.POINTER(C.c_float * 2)]
+    if hasattr(L, "slhip_pose_pnp"):                 # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_pose_pnp_check_params.argtypes = [C.c_void_p]
+        L.slhip_pose_pnp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PosePnpOut), C.c_void_p]
+        L.slhip_pose_pnp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PosePnpOut)]
+        L.slhip_pose_pnp_p3p_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_pose_pnp_timing_enable.argtypes = [C.c_int]
+        L.slhip_pose_pnp_timings.argtypes = [C.POINTER(C.c_float * 2)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

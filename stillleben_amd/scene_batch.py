@@ -563,6 +563,22 @@ class SceneBatch:
         return pose_vsd.evaluate(self.object_to_camera[s0:s0 + B], estimates, self.d_objects[s0 * nb:(s0 + B) * nb], surface,
                                  buffers.coord[:B], self.intrinsics(), **kw)
 
+    def pose_pnp(self, points, coord=None, **kw):
+        """sl.pose_pnp.solve on the point sets of a render (`points` = what points(...) returned, with its `pixel` and `coord`
+        outputs) with the batch's intrinsics, the Philox key of the view last placed and the first scene id of the batch as the
+        set id base: a PosePnP with one pose per set.  `coord`: float32 [n, K, 4] coordinates that replace the rendered ones
+        (a network's prediction; a correspondence counts when its w > 0).  `kw`: n_hypotheses, threshold_px, refine_iters,
+        min_inliers, outputs, init.  pose_pnp(...).dense(B, O, points.scene_global, points.slot) is the [B, O, 3, 4] that
+        pose_errors and pose_vsd take."""
+        from . import pose_pnp
+
+        for name in ("intrinsics", "seed", "set_id_base", "xyz", "per_set_intrinsics"):
+            if name in kw:
+                raise TypeError("SceneBatch.pose_pnp sets `%s` itself" % name)
+        key = _abi.view_key(int(self.params["seed_lo"]), int(self.params["seed_hi"]), self.view)
+        return pose_pnp.solve(points, coord=coord, intrinsics=self.intrinsics(), seed=key,
+                              set_id_base=int(self.params["scene_id_base"]), **kw)
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

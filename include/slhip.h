@@ -287,10 +287,16 @@ int slhip_render_ssao_skipped(const slhip_render_scratch* scratch, uint32_t n_sc
  * on `scratch` (same n_scenes, width, height): counts[0..5] = tiles per level, counts[6] = the end-of-band runs of the tap
  * kernel, counts[7] = those of them that held pixels of more than one level; synchronises.  Environment, read at every
  * slhip_render: SLHIP_SSAO_DEBUG=2 runs every tile at the full list, =3 keeps the levels and counts the end-of-band runs (they
- * are zero otherwise); SLHIP_SSAO_BAND_ROWS = rows per band of the tap kernel (a multiple of 16, default 16; placement only).  */
+ * are zero otherwise); SLHIP_SSAO_BAND_ROWS = rows per band of the tap kernel (a multiple of 16, default 16; placement only);
+ * SLHIP_SSAO_POOL=0: every wave of the tap kernel drains its own queues at the end of a band, instead of the four waves of a block
+ * draining theirs as one list (the same bits).  slhip_render_ssao_run_slots, also counted under SLHIP_SSAO_DEBUG=3 only: slots[0] = full runs of the tap
+ * kernel, slots[1] = the tap lane-slots they issued (taps of the list x 64), slots[2] = the tap lane-slots the end-of-band runs
+ * issued, slots[3] = those their pixels needed (each running lane's own list); synchronises.  */
 int slhip_render_ssao_level_tables(float rho[5], uint32_t counts[6], uint8_t taps[384]);
 int slhip_render_ssao_levels(const slhip_render_scratch* scratch, uint32_t n_scenes, uint32_t width, uint32_t height,
                              uint64_t counts[8], void* stream);
+int slhip_render_ssao_run_slots(const slhip_render_scratch* scratch, uint32_t n_scenes, uint32_t width, uint32_t height,
+                                uint64_t slots[4], void* stream);
 
 /* Bytes of each scratch buffer for a batch (host helper, no GPU needed).  `hdr` is sized for TWO float4 planes per scene: plane 0
  * = the fragment shader's linear colour (always written when rgb is asked for), plane 1 = the same after ambient occlusion, the

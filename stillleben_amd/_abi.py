@@ -499,6 +499,7 @@ def lib():
                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.slhip_render_ssao_skipped.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64 * 2), C.c_void_p]
     L.slhip_render_ssao_levels.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64 * 8), C.c_void_p]
+    L.slhip_render_ssao_run_slots.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64 * 4), C.c_void_p]
     L.slhip_render_ssao_level_tables.argtypes = [C.POINTER(C.c_float * 5), C.POINTER(C.c_uint32 * 6), C.POINTER(C.c_uint8 * 384)]
     L.slhip_settle_caps.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64 * 10), C.c_void_p]
     L.slhip_settle_timing_enable.argtypes = [C.c_int]

@@ -148,6 +148,18 @@ class Engine:
             _abi.check(self.L.slhip_render_ssao_levels(C.byref(a), buffers.B, W, H, C.byref(out), C.c_void_p(stream)), "slhip_render_ssao_levels")
         return [int(v) for v in out[:6]], int(out[6]), int(out[7])
 
+    def ssao_run_slots(self, buffers, W, H):
+        """(full runs, their tap lane-slots, tap lane-slots the end-of-band runs issued, those their pixels needed) of the render
+        that filled `buffers`, counted under SLHIP_SSAO_DEBUG=3 (slhip_render_ssao_run_slots; synchronises)."""
+        keep = buffers._keepalive[0]
+        a = _abi.RenderScratch()
+        a.d_ao = _ptr(keep["ao"])
+        out = (C.c_uint64 * 4)()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _abi.check(self.L.slhip_render_ssao_run_slots(C.byref(a), buffers.B, W, H, C.byref(out), C.c_void_p(stream)), "slhip_render_ssao_run_slots")
+        return tuple(int(v) for v in out)
+
     # ---- render ----------------------------------------------------------------------------
     def upload_records(self, arr):
         raw = np.frombuffer(arr.tobytes(), dtype=np.uint8) if arr.size else np.zeros(16, np.uint8)

@@ -30,6 +30,7 @@
 #include "slhip_common.h"
 #include "slhip_cubemap.h"
 #include "slhip_raster_walk.h"
+#include "slhip_ssao_pool.h"
 #include "slhip_tile_queue.h"
 
 // Occupancy ceilings of the render kernels (waves per SIMD; 0 = whatever the registers allow; build-time experiment knobs).  In
@@ -2426,6 +2427,7 @@ constexpr int kSsaoLevels = 6;
 constexpr float kSsaoRho[kSsaoLevels - 1] = {0.81f, 0.6f, 0.45f, 0.3f, 0.2f};
 __constant__ float c_ssao_level_kernel[kSsaoLevels * 192];
 struct SsaoLevelCounts { int n[kSsaoLevels]; };
+constexpr unsigned kSsaoStatWords = 2 + 2 * 4;      // the counters of k_ssao_tiled: two of 32 bits, then four of 64
 
 __global__ __launch_bounds__(256) void k_ssao_mask(const slhip_scene* __restrict__ scenes, int W, int H,
                                                   const float2* __restrict__ tiles, unsigned char* __restrict__ skip, int dbg,
@@ -2437,7 +2439,7 @@ __global__ __launch_bounds__(256) void k_ssao_mask(const slhip_scene* __restrict
     const float2* T = tiles + (size_t)scene * (TW * TH);
     unsigned char* S = skip + (size_t)scene * (TW * TH);
     const float* proj = scenes[scene].proj;
-    if (scene == 0 && threadIdx.x < 2) drain_stats[threadIdx.x] = 0u;      // (k_ssao_tiled counts its end-of-band runs there)
+    if (scene == 0 && threadIdx.x < kSsaoStatWords) drain_stats[threadIdx.x] = 0u;   // (k_ssao_tiled counts its runs there)
     // the rule is derived for a plain perspective projection (no skew, w = camera z): anything else runs every pixel
     const bool persp = proj[1] == 0.0f && proj[3] == 0.0f && proj[4] == 0.0f && proj[7] == 0.0f &&
                        proj[12] == 0.0f && proj[13] == 0.0f && proj[14] == 1.0f && proj[15] == 0.0f && proj[0] > 0.0f && proj[5] > 0.0f;
@@ -2482,16 +2484,29 @@ __global__ __launch_bounds__(256) void k_ssao_mask(const slhip_scene* __restrict
 // grid: scenes x bands of `band_rows` rows x 4 row classes; block = 4 waves = the 4 column classes of the same rows (their normal /
 // position fetches share cache lines).  A wave scans its class's pixels once, 64 candidates at a time, and queues those that need
 // taps by the level of their tile (the pixel index only: the run reads the normal again); a queue that holds 64 runs its level's
-// list.  At the end of the band the remainders go, from the highest level down, into common runs of 64, each with the list of the
-// highest level in it: ONE partial run per wave, not one per level.
+// list.  At the end of the band every queue is left with fewer than 64.  A wave alone has 640 candidates per band at 640 columns,
+// so its five remainders are a large part of its work, and drained wave by wave they go into runs that mix levels (each with the
+// list of the highest level in it) and a last run that is part empty.  `pool`: the block's four waves, which work on the same rows
+// and finish together, meet at ONE barrier and drain their 4 x 5 remainders as one list (slhip_ssao_pool.h), the highest level
+// first, in runs of 64 dealt out wave by wave: a run still has the list of its first (highest) entry, but of 20 remainders few
+// runs straddle a level, and only the block's last run is part empty.  Without it (SLHIP_SSAO_POOL=0) every wave drains its own.
+// Either way a pixel runs a list at least as long as its own: the same bits.  Measured on 512 C2 scenes (profiles/r17): the
+// per-wave drain's end-of-band runs issued 28.5 % of all tap lane-slots, 2.04 M per scene for pixels that needed 1.17 M; pooled
+// they issue 1.33 M, the kernel runs 5.54 M instead of 6.02 M VALU wave-instructions per scene and 12.0 instead of 13.0 ms per
+// 1024 scenes (0.3 ms of it: the scan skips its five ballots when no candidate needs taps).
+// `drain_stats` (SLHIP_SSAO_DEBUG=3): two 32-bit counters -- end-of-band runs, those of them with levels mixed -- and behind them
+// four of 64 bits: full runs, their tap lane-slots (n_taps x 64: issued = needed), the lane-slots the end-of-band runs issued, and
+// the lane-slots their pixels needed (each running lane's own list).
 __global__ __launch_bounds__(256) SLHIP_SSAO_KERNEL void k_ssao_tiled(const slhip_scene* __restrict__ scenes, unsigned n_scenes, int W, int H,
                                                     const float* __restrict__ cam, const float* __restrict__ nrm,
                                                     const float* __restrict__ zplane, float* __restrict__ ao,
                                                     const float* __restrict__ level_kern, SsaoLevelCounts level_n,
                                                     const unsigned char* __restrict__ skip, unsigned band_rows,
-                                                    unsigned* __restrict__ drain_stats)
+                                                    unsigned* __restrict__ drain_stats, int pool)
 {
+    static_assert(slhip_sp::kWaves == 4 && slhip_sp::kLevels == kSsaoLevels - 1 && slhip_sp::kQueueWords == 128, "slhip_ssao_pool.h describes s_q");
     __shared__ unsigned s_q[4][kSsaoLevels - 1][128];       // per wave and level 1.. : < 64 waiting + the <= 64 of one scan
+    __shared__ unsigned s_left[slhip_sp::kSegments];        // what each wave's queues hold at the end of the band: [wave][level - 1]
     const unsigned bands = ((unsigned)H + band_rows - 1u) / band_rows;
     unsigned scene, rest;
     if (!scene_block(bands * 4u, n_scenes, scene, rest)) return;       // (all blocks of a scene on one XCD: its z plane in ONE L2)
@@ -2522,9 +2537,41 @@ __global__ __launch_bounds__(256) SLHIP_SSAO_KERNEL void k_ssao_tiled(const slhi
     };
     unsigned pix_n, lvl_n; float4 n4_n;
     fetch(lane, pix_n, lvl_n, n4_n);
+    // one run: the lanes with a pixel run the taps of `list`
+    auto run_taps = [&](unsigned pix, bool valid, unsigned list) {
+        int n_taps = 0;
+#pragma unroll
+        for (int l = 1; l < kSsaoLevels; ++l)
+            if (list == (unsigned)l) n_taps = level_n.n[l];
+        if (valid) {
+            const int i = (int)(pix % (unsigned)W), j = (int)(pix / (unsigned)W);
+            A[pix] = ssao_pixel(proj, camS, W, H, i, j, N4[pix], C4[pix], level_kern + 192u * list, n_taps);
+        }
+    };
+    // the counters of one end-of-band run (only when asked for: SLHIP_SSAO_DEBUG=3); `own`: the level of the lane's pixel
+    auto count_drain_run = [&](unsigned list, bool valid, unsigned own) {
+        unsigned lowest = list, needed = 0;
+#pragma unroll
+        for (int l = kSsaoLevels - 1; l >= 1; --l) {
+            const unsigned n = (unsigned)__popcll(__ballot(valid && own == (unsigned)l));
+            if (n) lowest = (unsigned)l;
+            needed += n * (unsigned)level_n.n[l];
+        }
+        if (lane == 0u) {
+            unsigned long long* wide = reinterpret_cast<unsigned long long*>(drain_stats + 2);
+            unsigned issued = 0;
+#pragma unroll
+            for (int l = 1; l < kSsaoLevels; ++l)
+                if (list == (unsigned)l) issued = 64u * (unsigned)level_n.n[l];
+            atomicAdd(&drain_stats[0], 1u);
+            if (lowest != list) atomicAdd(&drain_stats[1], 1u);           // levels mixed in one run
+            atomicAdd(&wide[2], (unsigned long long)issued);
+            atomicAdd(&wide[3], (unsigned long long)needed);
+        }
+    };
     unsigned c0 = 0;
     for (;;) {
-        unsigned pix = 0, list = 0;
+        unsigned pix = 0, list = 0, own = 0;
         bool valid = false;
 #pragma unroll
         for (int l = 1; l < kSsaoLevels; ++l)
@@ -2535,6 +2582,15 @@ __global__ __launch_bounds__(256) SLHIP_SSAO_KERNEL void k_ssao_tiled(const slhi
             for (int l = 1; l < kSsaoLevels; ++l)
                 if (list == (unsigned)l) { cnt[l] -= 64u; pix = q[(l - 1) * 128 + cnt[l] + lane]; }
             valid = true;
+            if (drain_stats && lane == 0u) {
+                unsigned long long* wide = reinterpret_cast<unsigned long long*>(drain_stats + 2);
+                unsigned issued = 0;
+#pragma unroll
+                for (int l = 1; l < kSsaoLevels; ++l)
+                    if (list == (unsigned)l) issued = 64u * (unsigned)level_n.n[l];
+                atomicAdd(&wide[0], 1ull);
+                atomicAdd(&wide[1], (unsigned long long)issued);
+            }
         } else if (c0 < total) {
             // scan the next 64 candidates
             const unsigned px = pix_n, lvl = lvl_n;
@@ -2544,48 +2600,62 @@ __global__ __launch_bounds__(256) SLHIP_SSAO_KERNEL void k_ssao_tiled(const slhi
             fetch(c0 + lane, pix_n, lvl_n, n4_n);
             const bool need = in && lvl != 0u && !(n4.x == 0.0f && n4.y == 0.0f && n4.z == 0.0f);
             if (in && !need) A[px] = 1.0f;
+            if (__ballot(need) != 0ull) {                                 // (most scans of the open plane queue nothing)
 #pragma unroll
-            for (int l = 1; l < kSsaoLevels; ++l) {
-                const bool mine = need && lvl == (unsigned)l;
-                const unsigned long long m = __ballot(mine);
-                if (mine) q[(l - 1) * 128 + cnt[l] + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = px;
-                cnt[l] += (unsigned)__popcll(m);
+                for (int l = 1; l < kSsaoLevels; ++l) {
+                    const bool mine = need && lvl == (unsigned)l;
+                    const unsigned long long m = __ballot(mine);
+                    if (mine) q[(l - 1) * 128 + cnt[l] + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = px;
+                    cnt[l] += (unsigned)__popcll(m);
+                }
             }
             __builtin_amdgcn_wave_barrier();
             continue;
+        } else if (pool) {
+            break;                                                        // the remainders go to the block's common list (below)
         } else {
             // the end of the band: what is left, from the highest level down, 64 at a time
-            unsigned room = 64u, p = lane, lowest = 0;
+            unsigned room = 64u, p = lane;
 #pragma unroll
             for (int l = kSsaoLevels - 1; l >= 1; --l) {
                 const unsigned take = min(cnt[l], room);
                 if (take) {
                     if (!list) list = (unsigned)l;
-                    lowest = (unsigned)l;
                     cnt[l] -= take;
                     room -= take;
                     if (!valid) {
-                        if (p < take) { pix = q[(l - 1) * 128 + cnt[l] + p]; valid = true; }
+                        if (p < take) { pix = q[(l - 1) * 128 + cnt[l] + p]; valid = true; own = (unsigned)l; }
                         else p -= take;
                     }
                 }
             }
             if (!list) break;
-            if (drain_stats && lane == 0u) {                             // (only when asked for: SLHIP_SSAO_DEBUG=3)
-                atomicAdd(&drain_stats[0], 1u);
-                if (lowest != list) atomicAdd(&drain_stats[1], 1u);       // levels mixed in one run
-            }
+            if (drain_stats) count_drain_run(list, valid, own);
         }
         __builtin_amdgcn_wave_barrier();
-        int n_taps = 0;
+        run_taps(pix, valid, list);
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (!pool) return;
+    // The pooled drain.  Every wave of the block arrives here (the only early return, scene_block, is block-uniform) with fewer
+    // than 64 in each queue; nothing writes s_q after the barrier, so the runs need no further one.
+    if (lane == 0u) {
 #pragma unroll
-        for (int l = 1; l < kSsaoLevels; ++l)
-            if (list == (unsigned)l) n_taps = level_n.n[l];
-        if (valid) {
-            const int i = (int)(pix % (unsigned)W), j = (int)(pix / (unsigned)W);
-            A[pix] = ssao_pixel(proj, camS, W, H, i, j, N4[pix], C4[pix], level_kern + 192u * list, n_taps);
-        }
-        __builtin_amdgcn_wave_barrier();
+        for (int l = 1; l < kSsaoLevels; ++l) s_left[xc * slhip_sp::kLevels + (unsigned)(l - 1)] = cnt[l];
+    }
+    __syncthreads();
+    unsigned left[slhip_sp::kSegments];                                  // (uniform: scalar registers)
+#pragma unroll
+    for (unsigned s = 0; s < slhip_sp::kSegments; ++s) left[s] = __builtin_amdgcn_readfirstlane(s_left[s]);
+    const unsigned pooled = slhip_sp::total(left);                       // < 20 x 64
+    const unsigned* q_all = &s_q[0][0][0];
+    for (unsigned first = 64u * (unsigned)__builtin_amdgcn_readfirstlane(xc); first < pooled; first += 64u * slhip_sp::kWaves) {
+        unsigned list, own, word, word0;
+        slhip_sp::locate(left, first, list, word0);                      // the run's list: the level of its first entry
+        const bool valid = slhip_sp::locate(left, first + lane, own, word);
+        const unsigned pix = valid ? q_all[word] : 0u;
+        if (drain_stats) count_drain_run(list, valid, own);
+        run_taps(pix, valid, list);
     }
 }
 
@@ -2602,6 +2672,9 @@ __global__ __launch_bounds__(256) SLHIP_LIGHT_KERNEL void k_ssao_apply(const slh
     const unsigned blocks_per_scene = (unsigned)((P + 255) / 256);
     unsigned scene, blk;
     if (!scene_block(blocks_per_scene, n_scenes, scene, blk)) return;
+    // (256 consecutive pixels per block, a wave a 64 x 1 strip.  k_shade's placement -- a wave an 8 x 8 tile, so that the verdict
+    // below hangs on at most four tiles and the windows fall into a 12 x 12 patch -- was measured and is SLOWER: 3.10 against
+    // 2.89 ms per 1024 C2 scenes, profiles/r17.  A tile row is 32 bytes of the rgb target, not a line.)
     const unsigned pix = blk * 256 + threadIdx.x;
     if (pix >= P) return;
     const float* camS = zplane + (size_t)scene * ((size_t)(W + 2) * (H + 2));   // padded: texel (x, y) at [y + 1][x + 1]
@@ -2851,7 +2924,8 @@ extern "C" int slhip_render_ssao_level_tables(float rho[5], uint32_t counts[6], 
 }
 
 // layout of d_ao: [B][H][W] occlusion, [B][H + 2][W + 2] camera z, then (8-byte aligned) the SSAO tile records and skip bytes, then
-// (in the 16 spare bytes, 8-byte aligned) two counters of k_ssao_tiled: end-of-band runs, those of them with levels mixed
+// (in the spare bytes, 8-byte aligned) the counters of k_ssao_tiled: end-of-band runs, those of them with levels mixed, then four
+// of 64 bits (full runs, their tap lane-slots, the lane-slots the end-of-band runs issued and those their pixels needed)
 static inline uint64_t ssao_tiles_per_scene(uint32_t w, uint32_t h) { return (uint64_t)((w + 7) / 8) * ((h + 7) / 8); }
 static inline uint64_t ssao_tiles_offset(uint64_t B, uint32_t w, uint32_t h)
 {
@@ -2859,8 +2933,8 @@ static inline uint64_t ssao_tiles_offset(uint64_t B, uint32_t w, uint32_t h)
     return (b + 7u) & ~(uint64_t)7u;
 }
 
-constexpr uint64_t kSsaoScratchSpare = 16;      // bytes of d_ao behind the tile bytes
-static_assert(7 + 2 * sizeof(unsigned) <= kSsaoScratchSpare, "the two counters of k_ssao_tiled, 8-byte aligned, live in the spare bytes");
+constexpr uint64_t kSsaoScratchSpare = 48;      // bytes of d_ao behind the tile bytes
+static_assert(7 + kSsaoStatWords * sizeof(unsigned) <= kSsaoScratchSpare, "the counters of k_ssao_tiled, 8-byte aligned, live in the spare bytes");
 static inline uint64_t ssao_stats_offset(uint64_t B, uint32_t w, uint32_t h)
 {
     return (ssao_tiles_offset(B, w, h) + B * ssao_tiles_per_scene(w, h) * 9 + 7u) & ~(uint64_t)7u;
@@ -2927,6 +3001,27 @@ extern "C" int slhip_render_ssao_levels(const slhip_render_scratch* scratch, uin
     for (unsigned char b : h) counts[std::min<int>(b >> 1, kSsaoLevels - 1)] += 1;
     counts[6] = stats[0];
     counts[7] = stats[1];
+    return 0;
+}
+
+// The runs of k_ssao_tiled in that pass (counted only under SLHIP_SSAO_DEBUG=3, zero otherwise): slots[0] = full runs, slots[1] =
+// the tap lane-slots they issued (n_taps x 64, all of them needed), slots[2] = the tap lane-slots the end-of-band runs issued,
+// slots[3] = those their pixels needed (each running lane's own list).  Synchronises `stream`.
+extern "C" int slhip_render_ssao_run_slots(const slhip_render_scratch* scratch, uint32_t n_scenes, uint32_t width, uint32_t height,
+                                           uint64_t slots[4], void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!scratch || !scratch->d_ao || !slots) {
+        slhip::set_error("slhip_render_ssao_run_slots: null argument");
+        return -1;
+    }
+    for (int i = 0; i < 4; ++i) slots[i] = 0;
+    if (width % 32 != 0 || height % 16 != 0 || n_scenes == 0) return 0;
+    unsigned long long wide[4] = {0, 0, 0, 0};
+    const char* ao = reinterpret_cast<const char*>(scratch->d_ao);
+    SLHIP_CHECK(hipMemcpyAsync(wide, ao + ssao_stats_offset(n_scenes, width, height) + 2 * sizeof(unsigned), sizeof(wide), hipMemcpyDeviceToHost, stream));
+    SLHIP_CHECK(hipStreamSynchronize(stream));
+    for (int i = 0; i < 4; ++i) slots[i] = wide[i];
     return 0;
 }
 
@@ -3142,11 +3237,14 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
                 const float* d_level_table = nullptr;
                 SLHIP_CHECK(hipGetSymbolAddress((void**)&d_level_table, HIP_SYMBOL(c_ssao_level_kernel)));
                 // SLHIP_SSAO_DEBUG (read at every call): 1 = every tile skipped, 2 = every tile at the full list, 3 = the levels as they
-                // are, and k_ssao_tiled counts its end-of-band runs (slhip_render_ssao_levels; atomics no other render pays for)
+                // are, and k_ssao_tiled counts its runs (slhip_render_ssao_levels, slhip_render_ssao_run_slots; atomics no other render
+                // pays for).  SLHIP_SSAO_POOL=0 (read at every call): every wave drains its own remainders at the band's end, not
+                // the block's four together -- the in-library reference of the pooled drain.
+                const int ssao_pool = getenv("SLHIP_SSAO_POOL") ? atoi(getenv("SLHIP_SSAO_POOL")) : 1;
                 k_ssao_mask<<<n_scenes, 256, (size_t)(W / 8 + 1) * (H / 8 + 1) * 4, stream>>>(d_scenes, W, H, ssao_tiles, ssao_skip, ssao_dbg, drain_stats);
                 k_ssao_tiled<<<8u * ((n_scenes + 7u) / 8u) * bands * 4u, 256, 0, stream>>>(d_scenes, n_scenes, W, H, out->d_cam_coord, out->d_normals,
                                                                                    zpl, scratch->d_ao, d_level_table, ssao_level_tables().count, ssao_skip,
-                                                                                   band_rows, ssao_dbg == 3 ? drain_stats : nullptr);
+                                                                                   band_rows, ssao_dbg == 3 ? drain_stats : nullptr, ssao_pool != 0);
             } else
                 k_ssao<<<pix_blocks, 256, 0, stream>>>(d_scenes, n_scenes, W, H, out->d_cam_coord, out->d_normals, zpl, scratch->d_ao,
                                                        d_kernel_table);

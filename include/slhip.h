@@ -1364,6 +1364,101 @@ int slhip_pose_pnp_p3p_host(const float* uv, const float* xyz, const float* intr
 int slhip_pose_pnp_timing_enable(int on);
 int slhip_pose_pnp_timings(float ms_out[2]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Keypoint voting: one 2D position, with an uncertainty, per (set, keypoint) from a predicted field of
+ * per-pixel unit vectors -- PVNet's RANSAC voting layer, the step between the vector-field target
+ * (slhip_object_keypoints_field) and slhip_pose_pnp.  This project's addition, the reference has no
+ * counterpart.  All float32, one rounded IEEE operation at a time (no fma), only + - * / sqrt fabs and
+ * comparisons; csrc/slhip_vote_rules.h holds the rules for host and device, so slhip_keypoint_vote_host
+ * gives the device's outputs bit for bit.  DESIGN.md "Keypoint voting" states them operation by
+ * operation; in short, per set m and keypoint k:
+ *   1. valid list: voter j counts when its pixel lies in [0, W) x [0, H), its scene lies in the field
+ *      (dense mode; nothing is read otherwise), (vx, vy) is finite and l = sqrtf(vx*vx + vy*vy) > 0; then
+ *      d = (vx / l, vy / l), p = ((float)x + 0.5f, (float)y + 0.5f).  The valid ones are taken in ascending
+ *      j, n_valid of them; fewer than 2: SLHIP_VOTE_INSUFFICIENT.
+ *   2. hypothesis h draws Philox counter (set_id_base + m, 8, h, k) under (seed_lo, seed_hi)
+ *      ("Randomness" below); words 0 and 1 pick a and b, each min(n_valid - 1, (uint32_t)(uniform(x) *
+ *      (float)n_valid)).  Void when a == b, p_a == p_b, det = d_a.x*d_b.y - d_a.y*d_b.x has fabsf(det) <=
+ *      min_sin, or q is not finite; else s = ((p_b.x - p_a.x)*d_b.y - (p_b.y - p_a.y)*d_b.x) / det and
+ *      q = (p_a.x + s*d_a.x, p_a.y + s*d_a.y).
+ *   3. score: with e = q - p_j, dot = e.x*d.x + e.y*d.y, n2 = e.x*e.x + e.y*e.y, voter j is an inlier when
+ *      n2 == 0 or (dot > 0 and dot*dot >= (inlier_cos*inlier_cos) * n2).  A void hypothesis scores 0.  The
+ *      winner: highest count, ties to the lowest h.  A winner below min_inliers: SLHIP_VOTE_NO_MODEL.
+ *   4. distribution over the non-void hypotheses, w_h = (float)count_h / (float)n_valid: mean = (sum(w*q.x)
+ *      / sum(w), sum(w*q.y) / sum(w)); cov = the sums of (w*gx)*gx, (w*gx)*gy, (w*gy)*gy, g = q - mean, each
+ *      / sum(w).  Every sum in the order of the pose errors' means: lane h % 256 takes its hypotheses
+ *      upwards from 0.0f, the butterfly in a wave, ((w0 + w1) + w2) + w3.
+ *   5. refinement: one least-squares step on the winner's inliers of the valid list (lane i % 256):
+ *      n = (-d.y, d.x), c = n . (p - q) by line_offset of slhip_vote_rules.h (the differences, the products
+ *      and their sum formed error-free from rounded + - *, the lost parts added back smallest first: c is
+ *      the small rest of two products of the size of |p - q| and would otherwise keep their rounding); the
+ *      sums a00 n.x*n.x, a01 n.x*n.y, a11 n.y*n.y, b0 n.x*c, b1 n.y*c; det = a00*a11 - a01*a01 not finite or
+ *      not > 0: SLHIP_VOTE_REFINE_STOPPED and uv = q; else uv = (q.x + (b0*a11 - a01*b1) / det, q.y +
+ *      (a00*b1 - a01*b0) / det).
+ *   6. inliers and count of uv by rule 3 over the voters in their own order; fewer than the winner's
+ *      score: q and its figures with SLHIP_VOTE_REFINE_REJECTED.
+ * INSUFFICIENT and NO_MODEL give NaN uv, mean and cov, 0 inliers, best -2 and zero bits -- a position is
+ * never zero-filled.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_VOTE_POINTS_MAX      4096u
+#define SLHIP_VOTE_HYPOTHESES_MAX  1024u
+#define SLHIP_VOTE_OUT_UV        1u
+#define SLHIP_VOTE_OUT_N_INLIERS 2u
+#define SLHIP_VOTE_OUT_BEST      4u
+#define SLHIP_VOTE_OUT_FLAGS     8u
+#define SLHIP_VOTE_OUT_MEAN      16u
+#define SLHIP_VOTE_OUT_COV       32u
+#define SLHIP_VOTE_OUT_INLIERS   64u
+#define SLHIP_VOTE_INSUFFICIENT    1     /* flags: fewer than 2 valid voters                                    */
+#define SLHIP_VOTE_NO_MODEL        2     /* flags: no hypothesis reached min_inliers                            */
+#define SLHIP_VOTE_REFINE_STOPPED  4     /* flags: the normal equations were singular; uv is the winner's q     */
+#define SLHIP_VOTE_REFINE_REJECTED 8     /* flags: the refined position held fewer inliers; q is returned       */
+
+typedef struct {
+    uint32_t W, H;             /* the picture the pixels lie in, each side 1..32768                           */
+    uint32_t n_sets;           /* M                                                                           */
+    uint32_t n_points;         /* K voters per set, 2..SLHIP_VOTE_POINTS_MAX                                  */
+    uint32_t n_keypoints;      /* Kp, 1..SLHIP_KEYPOINTS_MAX                                                  */
+    uint32_t n_hypotheses;     /* Hy, 1..SLHIP_VOTE_HYPOTHESES_MAX                                            */
+    float inlier_cos;          /* in (0, 1): the smallest cosine between a voter's vector and its view of q   */
+    uint32_t min_inliers;      /* >= 2                                                                        */
+    float min_sin;             /* >= 0 and finite: the smallest |d_a x d_b| a sampled pair may have           */
+    uint32_t outputs;          /* SLHIP_VOTE_OUT_* bits, at least one                                         */
+    uint32_t seed_lo, seed_hi; /* Philox key                                                                  */
+    uint32_t set_id_base;      /* set m draws as set_id_base + m                                              */
+    uint32_t _pad[3];
+} slhip_keypoint_vote_params; /* 64 bytes */
+
+typedef struct {               /* read only when its bit is set; every pointer 4-byte aligned                 */
+    float* uv;                 /* f32 [M, Kp, 2], the keypoint's pixel position                               */
+    int32_t* n_inliers;        /* i32 [M, Kp]                                                                 */
+    int32_t* best;             /* i32 [M, Kp], the winning hypothesis; -2: none                               */
+    int32_t* flags;            /* i32 [M, Kp], SLHIP_VOTE_* flag bits                                         */
+    float* mean;               /* f32 [M, Kp, 2], the weighted mean of the hypotheses                         */
+    float* cov;                /* f32 [M, Kp, 3], their weighted covariance (xx, xy, yy)                      */
+    uint32_t* inliers;         /* u32 [M, Kp, ceil(K / 32)], bit j & 31 of word j >> 5                        */
+} slhip_keypoint_vote_out;
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_keypoint_vote_check_params(const slhip_keypoint_vote_params* params);
+/* d_pixel i16 [M, K, 2] (x, y), 4-byte aligned: the `pixel` of slhip_object_points_gather.  With d_scene (i32 [M]) non-null
+ * d_vectors is a dense field f32 [n_field_scenes, H, W, Kp, 2] (slhip_object_keypoints_field's layout, or a network's) and
+ * voter j of set m is read at (d_scene[m], y, x); a scene outside [0, n_field_scenes) or a pixel outside the picture reads
+ * nothing.  With d_scene null d_vectors is already gathered, f32 [M, K, Kp, 2] (networks that run on crops).  d_vectors is
+ * 8-byte aligned.  Every output named in params->outputs is written for every (set, keypoint), the others are not
+ * touched.  n_sets == 0 does nothing; null pointers (an output named in the mask included), misalignment, n_field_scenes < 1
+ * in dense mode and bad parameters are refused before anything touches the device.  One workgroup per (set, keypoint).
+ * Asynchronous on `stream`.                                                                                              */
+int slhip_keypoint_vote(const slhip_keypoint_vote_params* params, const int16_t* d_pixel, const float* d_vectors,
+                        const int32_t* d_scene, uint32_t n_field_scenes, const slhip_keypoint_vote_out* out, void* stream);
+/* The same rules on host arrays through csrc/slhip_vote_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_keypoint_vote_host(const slhip_keypoint_vote_params* params, const int16_t* h_pixel, const float* h_vectors,
+                             const int32_t* h_scene, uint32_t n_field_scenes, const slhip_keypoint_vote_out* out);
+/* Developer hook (tools/time_keypoint_vote.py): HIP events round the last slhip_keypoint_vote [0] and the last one that read
+ * a dense field [1] (-1: not run).                                                                                       */
+int slhip_keypoint_vote_timing_enable(int on);
+int slhip_keypoint_vote_timings(float ms_out[2]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).
@@ -1422,6 +1517,9 @@ int slhip_stream_destroy(void* stream);
  * Stream 7, correspondence samples (slhip_pose_pnp only; its key and set id base are the caller's, the set id stands where
  * the scene id does): index = the hypothesis h, x[0], x[1], x[2] pick the three correspondences of the minimal sample, x[3]
  * the fourth that disambiguates, each by the pick rule above over the n_valid correspondences ("Pose PnP" above).
+ * Stream 8, voter samples (slhip_keypoint_vote only; its key and set id base are the caller's, the set id stands where the
+ * scene id does, and the keypoint k stands where 0x51DE5EED does): index = the hypothesis h, x[0] and x[1] pick the two voters
+ * whose lines are intersected, each by the pick rule above over the n_valid voters ("Keypoint voting" above).
  * Views (slhip_synth_place_view): azimuth and elevation of view v >= 1 are the draw of view 0 -- stream 0, index 0, words 1 and
  * 2, the same scene id, the same formulas -- under the key (seed_lo + v * 0x9E3779B9, seed_hi + v * 0xBB67AE85), each sum
  * wrapping at 32 bits.  No other draw uses the view's key: the light's normals, the environment's gates and picks and everything

@@ -14,6 +14,7 @@ from stillleben_amd import ObjectStats  # noqa: F401  (additive: per-object visi
 from stillleben_amd import ObjectMasks  # noqa: F401  (additive: per-object masks as bit tiles and COCO run lengths)
 from stillleben_amd import bop  # noqa: F401  (additive: BOP entries of a SceneBatch's views)
 from stillleben_amd import pose_pnp, PosePnP  # noqa: F401  (additive: the pose of every set of 2D-3D correspondences)
+from stillleben_amd import keypoint_vote, KeypointVotes  # noqa: F401  (additive: predicted vector fields to 2D keypoints)
 
 __all__ = _impl.__all__
 for _name in ("camera_model", "diff", "extension", "losses", "profiling"):

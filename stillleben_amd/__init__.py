@@ -40,6 +40,8 @@ from . import pose_vsd  # noqa: F401  (additive: BOP's VSD against a batch's gro
 from .pose_vsd import PoseVSD, SurfaceBank  # noqa: F401
 from . import pose_pnp  # noqa: F401  (additive: the pose of every set of 2D-3D correspondences by P3P RANSAC and refinement)
 from .pose_pnp import PosePnP  # noqa: F401
+from . import keypoint_vote  # noqa: F401  (additive: predicted vector fields to 2D keypoints by RANSAC voting, PVNet's layer)
+from .keypoint_vote import KeypointVotes  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -51,6 +53,7 @@ __all__ = [
     'pose_error', 'ModelBank', 'PoseErrors',
     'pose_vsd', 'SurfaceBank', 'PoseVSD',
     'pose_pnp', 'PosePnP',
+    'keypoint_vote', 'KeypointVotes',
 ]
 
 

@@ -58,7 +58,10 @@ VSD_OUT_VSD, VSD_OUT_COUNTS, VSD_OUT_COST, VSD_OUT_FLAGS = 1, 2, 4, 8     # SLHI
 PNP_POINTS_MAX, PNP_HYPOTHESES_MAX, PNP_REFINE_MAX = 4096, 4096, 16          # SLHIP_PNP_*_MAX
 PNP_OUT_POSE, PNP_OUT_N_INLIERS, PNP_OUT_RMS, PNP_OUT_INLIERS, PNP_OUT_BEST, PNP_OUT_FLAGS = 1, 2, 4, 8, 16, 32      # SLHIP_PNP_OUT_*
 PNP_INSUFFICIENT, PNP_NO_MODEL, PNP_REFINE_STOPPED, PNP_REFINE_REJECTED = 1, 2, 4, 8      # SLHIP_PNP_*: the flag bits of a set
-REGIONS_MAX, REGION_NONE = 255, 255                                    # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
+VOTE_POINTS_MAX, VOTE_HYPOTHESES_MAX = 4096, 1024                            # SLHIP_VOTE_*_MAX
+VOTE_OUT_UV, VOTE_OUT_N_INLIERS, VOTE_OUT_BEST, VOTE_OUT_FLAGS, VOTE_OUT_MEAN, VOTE_OUT_COV, VOTE_OUT_INLIERS = 1, 2, 4, 8, 16, 32, 64      # SLHIP_VOTE_OUT_*
+VOTE_INSUFFICIENT, VOTE_NO_MODEL, VOTE_REFINE_STOPPED, VOTE_REFINE_REJECTED = 1, 2, 4, 8      # SLHIP_VOTE_*: the flag bits of a (set, keypoint)
+REGIONS_MAX, REGION_NONE = 255, 255                                   # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
 REGIONS_OUT_LOCAL, REGIONS_OUT_HISTOGRAM = 1, 2                        # SLHIP_REGIONS_OUT_*
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
@@ -354,6 +357,22 @@ class PosePnpOut(C.Structure):
                 ("flags", C.c_void_p)]
 
 
+# slhip_keypoint_vote_params (include/slhip.h), 64 bytes
+KEYPOINT_VOTE_PARAMS_DTYPE = np.dtype([
+    ("W", np.uint32), ("H", np.uint32), ("n_sets", np.uint32), ("n_points", np.uint32), ("n_keypoints", np.uint32),
+    ("n_hypotheses", np.uint32), ("inlier_cos", np.float32), ("min_inliers", np.uint32), ("min_sin", np.float32), ("outputs", np.uint32),
+    ("seed_lo", np.uint32), ("seed_hi", np.uint32), ("set_id_base", np.uint32), ("_pad", np.uint32, (3,)),
+])
+assert KEYPOINT_VOTE_PARAMS_DTYPE.itemsize == 64
+
+
+class KeypointVoteOut(C.Structure):
+    """slhip_keypoint_vote_out: the output pointers of slhip_keypoint_vote."""
+
+    _fields_ = [("uv", C.c_void_p), ("n_inliers", C.c_void_p), ("best", C.c_void_p), ("flags", C.c_void_p), ("mean", C.c_void_p),
+                ("cov", C.c_void_p), ("inliers", C.c_void_p)]
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -424,6 +443,7 @@ SYNTH_STREAM_ENV = 4     # Philox stream of the environment draws (include/slhip
 SYNTH_STREAM_CROP = 5    # Philox stream of the crop jitter (slhip_object_crops_select)
 SYNTH_STREAM_POINTS = 6  # Philox stream of the point ranks (slhip_object_points_gather)
 SYNTH_STREAM_PNP = 7     # Philox stream of the correspondence samples (slhip_pose_pnp)
+SYNTH_STREAM_VOTE = 8    # Philox stream of the voter samples (slhip_keypoint_vote)
 SYNTH_SAMPLE_DISTINCT = 1
 SYNTH_RANDOM_PBR = 2
 SYNTH_SHADOWS = 4
@@ -600,6 +620,12 @@ def lib():
         L.slhip_pose_pnp_p3p_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.slhip_pose_pnp_timing_enable.argtypes = [C.c_int]
         L.slhip_pose_pnp_timings.argtypes = [C.POINTER(C.c_float * 2)]
+    if hasattr(L, "slhip_keypoint_vote"):            # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_keypoint_vote_check_params.argtypes = [C.c_void_p]
+        L.slhip_keypoint_vote.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(KeypointVoteOut), C.c_void_p]
+        L.slhip_keypoint_vote_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(KeypointVoteOut)]
+        L.slhip_keypoint_vote_timing_enable.argtypes = [C.c_int]
+        L.slhip_keypoint_vote_timings.argtypes = [C.POINTER(C.c_float * 2)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

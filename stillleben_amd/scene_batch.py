@@ -579,6 +579,31 @@ class SceneBatch:
         return pose_pnp.solve(points, coord=coord, intrinsics=self.intrinsics(), seed=key,
                               set_id_base=int(self.params["scene_id_base"]), **kw)
 
+    def keypoint_votes(self, points, field, scenes=None, **kw):
+        """sl.keypoint_vote.vote on the point sets of a render (`points` = what points(...) returned, with its `pixel` output)
+        and a predicted vector field float32 [count, H, W, Kp, 2] in the layout of ObjectKeypoints.field, with the Philox key
+        of the view last placed and the first scene id of the batch as the set id base: a KeypointVotes with one position per
+        (set, keypoint).  `scenes`: the (first, count) the field was made for -- picture 0 of the field is scene `first` of the
+        points' render chunk; default: the field starts at the chunk's first scene.  The result carries the class of every
+        set's object from the batch's object records, so votes.correspondences(bank) is what pose_pnp takes.  `kw`:
+        n_hypotheses, inlier_cos, min_inliers, min_sin, outputs."""
+        from . import keypoint_vote
+
+        for name in ("seed", "set_id_base", "scene", "vectors", "size"):
+            if name in kw:
+                raise TypeError("SceneBatch.keypoint_votes sets `%s` itself" % name)
+        if points.pixel is None:
+            raise RuntimeError("keypoint_vote: the ObjectPoints need their `pixel` output")
+        first = 0 if scenes is None else int(scenes[0])
+        key = _abi.view_key(int(self.params["seed_lo"]), int(self.params["seed_hi"]), self.view)
+        out = keypoint_vote.vote(points, field=field, scene=points.scene - first, seed=key,
+                                 set_id_base=int(self.params["scene_id_base"]), **kw)
+        if points.scene_global is not None:
+            nb = self.n_scenes * self.n_objects * _abi.SYNTH_OBJECT_DTYPE.itemsize
+            asset = self.d_objects[:nb].view(torch.int32).view(self.n_scenes, self.n_objects, -1)[..., 0]
+            out.classes = asset[points.scene_global.long(), (points.slot - 1).long()]
+        return out
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

@@ -599,6 +599,9 @@ int slhip_overlap_any(const slhip_settle_scene* d_scenes, uint32_t n_scenes,
  * sl.diff half (replaces python/src/diff.cu + bridge_diff.cpp and fuses diff.py:355-523)
  * ------------------------------------------------------------------------------------------- */
 
+/* Every entry of this half returns -1 with an error text, before any launch, for H <= 0, W <= 0 or H * W > 0x7fffffff
+ * (pixels are indexed with int), and the pose backward for more than 256 objects (its accumulators live in LDS).   */
+
 /* generate_sobel_valid_mask (bridge_diff.cpp:13-69, CPU-loop semantics: the 1-px border stays
  * valid).  d_inst i16[H,W]; d_depth f32 with `depth_stride` floats between pixels (1 for a
  * dense [H,W] image, 4 to read channel 3 of the coordinate target in place); d_valid u8[H,W].  */

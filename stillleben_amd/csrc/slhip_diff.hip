@@ -14,7 +14,7 @@ __global__ __launch_bounds__(256) void k_sobel_valid(const int16_t* __restrict__
                                                      int dstride, int H, int W, uint8_t* __restrict__ valid)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= H * W) return;
+    if ((unsigned)p >= (unsigned)(H * W)) return;   // unsigned: the last block of an image near 2^31 pixels wraps p
     {   // blockIdx.y = image of a batch (pose hypotheses): [K, H, W] planes one after the other
         const size_t img = (size_t)blockIdx.y * H * W;
         inst += img; depth += img * dstride; valid += img;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void k_dilate(const uint8_t* __restrict__ mask
                                                 uint8_t* __restrict__ out_mask, float* __restrict__ out_coords)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= H * W) return;
+    if ((unsigned)p >= (unsigned)(H * W)) return;
     const int h = p / W, w = p % W;
     uint8_t om = 0;
     float cx = 0.0f, cy = 0.0f, cz = 0.0f;
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void k_image_gradients(const uint8_t* __restri
                                                          int H, int W, float* __restrict__ grad_x, float* __restrict__ grad_y)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= H * W) return;
+    if ((unsigned)p >= (unsigned)(H * W)) return;
     float gx[3], gy[3];
     pixel_gradients(rgb, p / W, p % W, H, W, gx, gy);
     const bool v = valid[p] != 0;
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void k_vertex_backward(const uint8_t* __restri
                                                          int H, int W, float* __restrict__ gv, float* __restrict__ gc)
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= H * W) return;
+    if ((unsigned)p >= (unsigned)(H * W)) return;
     const size_t N = (size_t)H * W;
     float outv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, outc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int16_t id = inst[p];
@@ -273,13 +273,17 @@ __global__ __launch_bounds__(256) void k_vertex_backward(const uint8_t* __restri
     }
 }
 
+// every kernel here indexes pixels with int and launches (H * W + 255) / 256 blocks
+inline bool bad_extent(int H, int W) { return H <= 0 || W <= 0 || (size_t)H * W > 0x7fffffffu; }
+inline unsigned pixel_blocks(int H, int W) { return (unsigned)(((size_t)H * W + 255) / 256); }
+
 }  // namespace
 
 extern "C" int slhip_diff_sobel_valid(const int16_t* d_inst, const float* d_depth, int depth_stride, int H, int W,
                                       uint8_t* d_valid, void* stream)
 {
-    if (!d_inst || !d_depth || !d_valid || H <= 0 || W <= 0) { slhip::set_error("slhip_diff_sobel_valid: bad argument"); return -1; }
-    k_sobel_valid<<<(H * W + 255) / 256, 256, 0, (hipStream_t)stream>>>(d_inst, d_depth, depth_stride, H, W, d_valid);
+    if (!d_inst || !d_depth || !d_valid || bad_extent(H, W)) { slhip::set_error("slhip_diff_sobel_valid: bad argument"); return -1; }
+    k_sobel_valid<<<pixel_blocks(H, W), 256, 0, (hipStream_t)stream>>>(d_inst, d_depth, depth_stride, H, W, d_valid);
     SLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -288,7 +292,9 @@ extern "C" int slhip_diff_dilate(const uint8_t* d_mask, const uint8_t* d_valid, 
                                  int H, int W, uint8_t* d_out_mask, float* d_out_coords, void* stream)
 {
     if (!d_mask || !d_valid || !d_coords || !d_out_mask || !d_out_coords) { slhip::set_error("slhip_diff_dilate: null argument"); return -1; }
-    k_dilate<<<(H * W + 255) / 256, 256, 0, (hipStream_t)stream>>>(d_mask, d_valid, d_coords, coord_stride, H, W, d_out_mask, d_out_coords);
+    if (bad_extent(H, W)) { slhip::set_error("slhip_diff_dilate: bad sizes (H %d, W %d)", H, W); return -1; }
+    if (coord_stride < 3) { slhip::set_error("slhip_diff_dilate: coord_stride %d, need at least 3 floats per pixel", coord_stride); return -1; }
+    k_dilate<<<pixel_blocks(H, W), 256, 0, (hipStream_t)stream>>>(d_mask, d_valid, d_coords, coord_stride, H, W, d_out_mask, d_out_coords);
     SLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -297,7 +303,8 @@ extern "C" int slhip_diff_image_gradients(const uint8_t* d_rgb, const uint8_t* d
                                           float* d_grad_y, void* stream)
 {
     if (!d_rgb || !d_valid || !d_grad_x || !d_grad_y) { slhip::set_error("slhip_diff_image_gradients: null argument"); return -1; }
-    k_image_gradients<<<(H * W + 255) / 256, 256, 0, (hipStream_t)stream>>>(d_rgb, d_valid, H, W, d_grad_x, d_grad_y);
+    if (bad_extent(H, W)) { slhip::set_error("slhip_diff_image_gradients: bad sizes (H %d, W %d)", H, W); return -1; }
+    k_image_gradients<<<pixel_blocks(H, W), 256, 0, (hipStream_t)stream>>>(d_rgb, d_valid, H, W, d_grad_x, d_grad_y);
     SLHIP_LAUNCH_CHECK();
     return 0;
 }
@@ -312,11 +319,12 @@ extern "C" int slhip_diff_pose_backward(const uint8_t* d_rgb, const float* d_coo
         slhip::set_error("slhip_diff_pose_backward: null argument");
         return -1;
     }
+    if (bad_extent(H, W)) { slhip::set_error("slhip_diff_pose_backward: bad sizes (H %d, W %d)", H, W); return -1; }
     if (n_obj <= 0) return 0;
     if (n_obj > kMaxDiffObjects) { slhip::set_error("slhip_diff_pose_backward: at most %d objects", kMaxDiffObjects); return -1; }
     Mat4 P;
     for (int i = 0; i < 16; ++i) P.m[i] = h_proj[i];
-    const int blocks = (H * W + 255) / 256;
+    const unsigned blocks = pixel_blocks(H, W);
     k_sobel_valid<<<blocks, 256, 0, stream>>>(d_inst, d_coord + 3, 4, H, W, d_valid);
     SLHIP_CHECK(hipMemsetAsync(d_acc, 0, sizeof(double) * 6 * n_obj, stream));
     k_pose_backward<<<blocks, 256, 0, stream>>>(d_rgb, d_coord, d_inst, d_valid, d_grad_img, P, d_poses, d_obj_inst, n_obj, H, W, d_acc, 0);
@@ -339,12 +347,13 @@ extern "C" int slhip_diff_pose_backward_batch(const uint8_t* d_rgb, const float*
         slhip::set_error("slhip_diff_pose_backward_batch: null argument");
         return -1;
     }
+    if (bad_extent(H, W)) { slhip::set_error("slhip_diff_pose_backward_batch: bad sizes (H %d, W %d)", H, W); return -1; }
     if (n_obj <= 0 || n_hyp <= 0) return 0;
     if (n_obj > kMaxDiffObjects) { slhip::set_error("slhip_diff_pose_backward_batch: at most %d objects", kMaxDiffObjects); return -1; }
     if (n_hyp > 65535) { slhip::set_error("slhip_diff_pose_backward_batch: at most 65535 hypotheses per call"); return -1; }
     Mat4 P;
     for (int i = 0; i < 16; ++i) P.m[i] = h_proj[i];
-    const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)n_hyp);
+    const dim3 grid(pixel_blocks(H, W), (unsigned)n_hyp);
     k_sobel_valid<<<grid, 256, 0, stream>>>(d_inst, d_coord + 3, 4, H, W, d_valid);
     SLHIP_CHECK(hipMemsetAsync(d_acc, 0, sizeof(double) * 6 * (size_t)n_obj * n_hyp, stream));
     k_pose_backward<<<grid, 256, 0, stream>>>(d_rgb, d_coord, d_inst, d_valid, d_grad_img, P, d_poses, d_obj_inst, n_obj, H, W, d_acc,
@@ -366,13 +375,13 @@ extern "C" int slhip_diff_vertex_backward(const uint8_t* d_rgb, const float* d_c
         slhip::set_error("slhip_diff_vertex_backward: null argument");
         return -1;
     }
-    if (H <= 0 || W <= 0 || n_obj < 0) {
+    if (bad_extent(H, W) || n_obj < 0) {
         slhip::set_error("slhip_diff_vertex_backward: bad sizes");
         return -1;
     }
     Mat4 P;
     for (int i = 0; i < 16; ++i) P.m[i] = h_proj[i];
-    const int blocks = (H * W + 255) / 256;
+    const unsigned blocks = pixel_blocks(H, W);
     k_sobel_valid<<<blocks, 256, 0, stream>>>(d_inst, d_coord + 3, 4, H, W, d_valid);
     k_vertex_backward<<<blocks, 256, 0, stream>>>(d_rgb, d_coord, d_inst, d_valid, d_bary, d_grad_img, P, d_poses, d_obj_inst,
                                                   n_obj, H, W, d_grad_vertices, d_grad_colors);

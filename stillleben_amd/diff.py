@@ -32,6 +32,43 @@ def _stream(eng):
     return C.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream)
 
 
+_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _check_gbuffer(rgb, coord, inst, batch=False):
+    """The layouts the kernels of csrc/slhip_diff.hip assume, checked before a pointer leaves Python: rgb uint8[H,W,4],
+    coordDepth float32[H,W,4] (None where the call reads none), instance int16[H,W] or [H,W,1]; with `batch` a leading K on all
+    of them.  An integer instance image of another width is converted to int16 when its values fit (as the native stencils
+    convert theirs); anything else raises ValueError naming the argument.  Returns (rgb, coord, instance int16[(K,)H,W],
+    ((K,)H,W)); works on tensors of any device."""
+    nd = 4 if batch else 3
+    form = "[K,H,W" if batch else "[H,W"
+    if rgb.dtype != torch.uint8 or rgb.dim() != nd or rgb.shape[-1] != 4:
+        raise ValueError("rgb must be uint8%s,4], not %s%s" % (form, rgb.dtype, list(rgb.shape)))
+    lead = tuple(rgb.shape[:-1])
+    if coord is not None and (coord.dtype != torch.float32 or tuple(coord.shape) != lead + (4,)):
+        raise ValueError("coordDepth must be float32%s, not %s%s" % (list(lead + (4,)), coord.dtype, list(coord.shape)))
+    if inst.dim() == nd and inst.shape[-1] == 1:
+        inst = inst.squeeze(-1)
+    if inst.dtype not in _INT_DTYPES or tuple(inst.shape) != lead:
+        raise ValueError("instance must be int16%s or %s, not %s%s" % (list(lead), list(lead + (1,)), inst.dtype, list(inst.shape)))
+    if inst.dtype != torch.int16:
+        if inst.numel() and (int(inst.min()) < -32768 or int(inst.max()) > 32767):
+            raise ValueError("instance (%s) holds values that do not fit int16" % inst.dtype)
+        inst = inst.to(torch.int16)
+    return rgb, coord, inst, lead
+
+
+def _check_grad_image(g, H, W, K=None):
+    """grad_objective_wrt_rnd_img is [3,H,W], or with K hypotheses also [K,3,H,W]: True for the per-hypothesis form."""
+    if tuple(g.shape) == (3, H, W):
+        return False
+    if K is not None and tuple(g.shape) == (K, 3, H, W):
+        return True
+    raise ValueError("grad_objective_wrt_rnd_img must be 3x%dx%d%s, not %s" % (H, W, "" if K is None else " or %dx3x%dx%d" % (K, H, W),
+                                                                                 list(g.shape)))
+
+
 def _native():
     """libstillleben_diff_python: the reference's extension module for these two functions (bridge_diff.cpp:160-180), here
     pybind11 host C++ over the C-ABI (csrc/py/diff_module.cpp).  No fallback: a missing build is an error."""
@@ -57,12 +94,14 @@ def dilate_object_mask(object_mask, sobel_valid_mask, coordinates):
 def compute_image_space_gradients(scene, render_result):
     """diff.py:73-127 -> (grad_x [3,H,W], grad_y [3,H,W], sobel_valid_mask bool[H,W])."""
     eng = engine()
-    rgb = render_result.rgb()
+    rgb, _, inst, (H, W) = _check_gbuffer(render_result.rgb(), None, render_result.instance_index())
     out_dev = rgb.device
-    H, W = rgb.shape[:2]
+    depth = render_result.depth()
+    if not depth.is_floating_point() or tuple(depth.shape) != (H, W):
+        raise ValueError("depth must be float32[%d,%d], not %s%s" % (H, W, depth.dtype, list(depth.shape)))
     with Timer('sobel_valid_mask'):
-        inst = render_result.instance_index().squeeze(-1).to(eng.device).contiguous()
-        depth = render_result.depth().to(eng.device).contiguous()
+        inst = inst.to(eng.device).contiguous()
+        depth = depth.to(eng.device, torch.float32).contiguous()
         valid = torch.empty((H, W), dtype=torch.uint8, device=eng.device)
         with torch.cuda.device(eng.device):
             _abi.check(eng.L.slhip_diff_sobel_valid(_p(inst), _p(depth), 1, H, W, _p(valid), _stream(eng)),
@@ -86,13 +125,10 @@ def backpropagate_gradient_to_poses(scene, render_result, grad_objective_wrt_rnd
     out = torch.zeros(n, 6)
     if n == 0:
         return out
-    rgb = render_result.rgb().to(eng.device).contiguous()
-    H, W = rgb.shape[:2]
-    coord = render_result.coordDepth().to(eng.device).contiguous()
-    inst = render_result.instance_index().squeeze(-1).to(eng.device).contiguous()
+    rgb, coord, inst, (H, W) = _check_gbuffer(render_result.rgb(), render_result.coordDepth(), render_result.instance_index())
+    _check_grad_image(grad_objective_wrt_rnd_img, H, W)
+    rgb, coord, inst = (t.to(eng.device).contiguous() for t in (rgb, coord, inst))
     g = grad_objective_wrt_rnd_img.to(eng.device, torch.float32).contiguous()
-    if tuple(g.shape) != (3, H, W):
-        raise ValueError("grad_objective_wrt_rnd_img must be 3xHxW")
     poses = torch.stack([o.pose() for o in objs]).to(eng.device, torch.float32).contiguous()
     ids = torch.tensor([o.instance_index for o in objs], dtype=torch.int32, device=eng.device)
     P = np.ascontiguousarray(scene.projection_matrix().numpy(), dtype=np.float32)
@@ -172,7 +208,13 @@ def pose_backward_batch_on_buffers(scene, buf, hyp, g):
     objs = scene.objects
     n, K = len(objs), hyp.shape[0]
     W, H = scene.viewport
-    per_hyp_grad = g.dim() == 4
+    rgb, coord, inst, lead = _check_gbuffer(buf.rgb, buf.coord, buf.instance, batch=True)
+    if lead != (K, H, W):
+        raise ValueError("rgb, coordDepth and instance of %d hypotheses at viewport %dx%d must lead with [%d,%d,%d], not %s"
+                         % (K, W, H, K, H, W, list(lead)))
+    per_hyp_grad = _check_grad_image(g, H, W, K)
+    rgb, coord, inst = (t.to(eng.device).contiguous() for t in (rgb, coord, inst))
+    g = g.to(eng.device, torch.float32).contiguous()
     d_poses = torch.from_numpy(np.ascontiguousarray(hyp, dtype=np.float32)).to(eng.device)
     ids = torch.tensor([o.instance_index for o in objs], dtype=torch.int32, device=eng.device)
     P = np.ascontiguousarray(scene.projection_matrix().numpy(), dtype=np.float32)
@@ -180,7 +222,7 @@ def pose_backward_batch_on_buffers(scene, buf, hyp, g):
     acc = torch.empty(K * 6 * n, dtype=torch.float64, device=eng.device)
     res = torch.empty((K, n, 6), dtype=torch.float32, device=eng.device)
     with torch.cuda.device(eng.device):
-        st = eng.L.slhip_diff_pose_backward_batch(_p(buf.rgb), _p(buf.coord), _p(buf.instance), _p(g), 3 * H * W if per_hyp_grad else 0,
+        st = eng.L.slhip_diff_pose_backward_batch(_p(rgb), _p(coord), _p(inst), _p(g), 3 * H * W if per_hyp_grad else 0,
                                                   C.c_void_p(P.ctypes.data), _p(d_poses), _p(ids), n, K, H, W, _p(valid), _p(acc),
                                                   _p(res), _stream(eng))
     _abi.check(st, "slhip_diff_pose_backward_batch")
@@ -194,17 +236,14 @@ def bp_to_vertices_and_colors(scene, render_result, grad_objective_wrt_rnd_img, 
     f32[3P,3] and -d objective / d colour f32[3P,3] (barycentric-weighted, ready for Mesh.update_*)."""
     eng = engine()
     objs = scene.objects
-    rgb = render_result.rgb().to(eng.device).contiguous()
-    H, W = rgb.shape[:2]
-    out_dev = render_result.rgb().device
+    rgb, coord, inst, (H, W) = _check_gbuffer(render_result.rgb(), render_result.coordDepth(), render_result.instance_index())
+    _check_grad_image(grad_objective_wrt_rnd_img, H, W)
+    out_dev = rgb.device
+    rgb, coord, inst = (t.to(eng.device).contiguous() for t in (rgb, coord, inst))
     g = grad_objective_wrt_rnd_img.to(eng.device, torch.float32).contiguous()
-    if tuple(g.shape) != (3, H, W):
-        raise ValueError("grad_objective_wrt_rnd_img must be 3xHxW")
     vertex_index_2_bp, grad_vertices_2_bp, grad_colors_2_bp = [], [], []
     if not objs:
         return vertex_index_2_bp, grad_vertices_2_bp, grad_colors_2_bp
-    coord = render_result.coordDepth().to(eng.device).contiguous()
-    inst = render_result.instance_index().squeeze(-1).to(eng.device).contiguous()
     bary = render_result.barycentric_coeffs().to(eng.device, torch.float32)
     if bary.shape[-1] == 3:
         bary = torch.cat([bary, torch.zeros_like(bary[..., :1])], dim=-1)

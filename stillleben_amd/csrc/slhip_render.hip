@@ -3095,18 +3095,21 @@ extern "C" int slhip_render(const slhip_mesh_pool* pool, const slhip_scene* d_sc
     if (ssao) {
         int dev = 0;
         SLHIP_CHECK(hipGetDevice(&dev));
-        if (dev < 16 && !g_ssao_tables_uploaded[dev]) {
-            SLHIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_ssao_noise), k_ssao_noise_host, sizeof(float) * 48, 0,
-                                               hipMemcpyHostToDevice, stream));
-            SLHIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_ssao_kernel), k_ssao_kernel_host, sizeof(float) * 192, 0,
-                                               hipMemcpyHostToDevice, stream));
+        // Once per device, and BLOCKING: the tables are process-wide, the flag is read by calls on every stream.  An asynchronous
+        // copy on the first caller's stream orders the tables before that stream's k_ssao* only -- the first render of a second
+        // stream could read them before they had landed.  The copies below are complete when they return, and only then is the
+        // flag set (a one-time host cost of the process's first SSAO render; a device beyond the flags uploads at every call).
+        if (dev < 0 || dev >= 16 || !g_ssao_tables_uploaded[dev]) {
             const SsaoLevelTables& lt = ssao_level_tables();
             if (lt.count.n[0] != 0) {
                 slhip::set_error("slhip_render: the first SSAO level threshold does not cover the longest kernel sample");
                 return -1;
             }
-            SLHIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_ssao_level_kernel), lt.kern, sizeof(lt.kern), 0, hipMemcpyHostToDevice, stream));
-            g_ssao_tables_uploaded[dev] = true;
+            SLHIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_ssao_noise), k_ssao_noise_host, sizeof(float) * 48, 0, hipMemcpyHostToDevice));
+            SLHIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_ssao_kernel), k_ssao_kernel_host, sizeof(float) * 192, 0, hipMemcpyHostToDevice));
+            SLHIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_ssao_level_kernel), lt.kern, sizeof(lt.kern), 0, hipMemcpyHostToDevice));
+            SLHIP_CHECK(hipStreamSynchronize(nullptr));      // (the copies ran on the null stream: nothing of them is in flight)
+            if (dev >= 0 && dev < 16) g_ssao_tables_uploaded[dev] = true;
         }
     }
 

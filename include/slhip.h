@@ -1462,6 +1462,158 @@ int slhip_keypoint_vote_host(const slhip_keypoint_vote_params* params, const int
 int slhip_keypoint_vote_timing_enable(int on);
 int slhip_keypoint_vote_timings(float ms_out[2]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Keypoint voting in 3D: one camera-frame position, with an uncertainty, per (set, keypoint) from
+ * per-point predicted 3D offsets (the layout of ObjectKeypoints.offsets) -- the decoder of PVN3D /
+ * FFB6D, by mean shift over the candidates and the mode with the most support.  This project's addition,
+ * the reference has no counterpart.  All float32, one rounded IEEE operation at a time (no fma), only
+ * + - * / and comparisons (no exp: the kernel of the mean shift is compact, not Gaussian);
+ * csrc/slhip_vote3d_rules.h holds the rules for host and device, so slhip_keypoint_vote3d_host gives the
+ * device's outputs bit for bit.  Nothing is random.  Per set m and keypoint k, with h = bandwidth,
+ * h2 = h*h, inv_h2 = 1 / (h*h), tol2 = tol*tol:
+ *   1. candidate c_j = (camera_j.x + offset_jk.x, .y + .y, .z + .z), valid when camera_j.w != 0 and the three
+ *      sums are finite.  The valid ones keep their ascending order in j, n_valid of them; none:
+ *      SLHIP_VOTE3D_INSUFFICIENT.
+ *   2. seeds: S_eff = min(n_seeds, n_valid); seed s starts at the valid candidate of rank
+ *      ((2 s + 1) * n_valid) / (2 * S_eff) in integers -- with n_seeds >= n_valid every candidate is a seed.
+ *   3. one step of seed x: over the valid candidates in ascending order, one after the other from 0.0f
+ *      (acc = acc + term): d = c_j - x per component, t = ((d.x*d.x + d.y*d.y) + d.z*d.z) * inv_h2,
+ *      w = t < 1 ? 1 - t : 0, and the four sums of w, w*d.x, w*d.y, w*d.z.  Then m = (sum w*d) / (sum w) per
+ *      component and x = x + m.  The seed stops when (m.x*m.x + m.y*m.y) + m.z*m.z <= tol2, or after
+ *      max_iters steps.  (sum w > 0 for a seed that started on a candidate: slhip_vote3d_rules.h.)
+ *   4. support of a finished seed: the valid candidates with ((d.x*d.x + d.y*d.y) + d.z*d.z) <= h2.  The
+ *      winner: highest support, ties to the lowest s.  A winner below min_support: SLHIP_VOTE3D_NO_MODEL.
+ *      A winner that took max_iters steps without stopping: SLHIP_VOTE3D_NOT_CONVERGED, its outputs are
+ *      written all the same.
+ *   5. over the winner's supporters: mean = sum(c) / (float)n_support per component; cov = the sums of
+ *      g.x*g.x, g.x*g.y, g.x*g.z, g.y*g.y, g.y*g.z, g.z*g.z, g = c - mean, each / (float)n_support.  Every
+ *      sum in the order of the pose errors' means over the valid list: lane i % 256 takes its supporters
+ *      i upwards from 0.0f, the butterfly in a wave, ((w0 + w1) + w2) + w3.
+ * INSUFFICIENT and NO_MODEL give NaN xyz, mean and cov, 0 supporters, best -2, 0 iterations and zero bits --
+ * a position is never zero-filled.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_VOTE3D_POINTS_MAX  4096u
+#define SLHIP_VOTE3D_SEEDS_MAX   1024u
+#define SLHIP_VOTE3D_ITERS_MAX   64u
+#define SLHIP_VOTE3D_OUT_XYZ       1u
+#define SLHIP_VOTE3D_OUT_N_SUPPORT 2u
+#define SLHIP_VOTE3D_OUT_BEST      4u
+#define SLHIP_VOTE3D_OUT_ITERS     8u
+#define SLHIP_VOTE3D_OUT_FLAGS     16u
+#define SLHIP_VOTE3D_OUT_MEAN      32u
+#define SLHIP_VOTE3D_OUT_COV       64u
+#define SLHIP_VOTE3D_OUT_SUPPORT   128u
+#define SLHIP_VOTE3D_INSUFFICIENT  1     /* flags: no valid voter                                               */
+#define SLHIP_VOTE3D_NO_MODEL      2     /* flags: no mode reached min_support                                  */
+#define SLHIP_VOTE3D_NOT_CONVERGED 4     /* flags: the winner took max_iters steps without meeting tol          */
+
+typedef struct {
+    uint32_t n_sets;           /* M                                                                           */
+    uint32_t n_points;         /* K voters per set, 1..SLHIP_VOTE3D_POINTS_MAX                                */
+    uint32_t n_keypoints;      /* Kp, 1..SLHIP_KEYPOINTS_MAX                                                  */
+    uint32_t n_seeds;          /* S, 1..SLHIP_VOTE3D_SEEDS_MAX                                                */
+    float bandwidth;           /* h > 0 and finite, in the unit of the camera points (metres)                 */
+    uint32_t max_iters;        /* 1..SLHIP_VOTE3D_ITERS_MAX                                                   */
+    float tol;                 /* >= 0 and finite: a seed stops when its shift squared is <= tol*tol          */
+    uint32_t min_support;      /* >= 1                                                                        */
+    uint32_t outputs;          /* SLHIP_VOTE3D_OUT_* bits, at least one                                       */
+    uint32_t _pad[7];
+} slhip_keypoint_vote3d_params; /* 64 bytes */
+
+typedef struct {               /* read only when its bit is set; every pointer 4-byte aligned                 */
+    float* xyz;                /* f32 [M, Kp, 3], the winner's mode in the camera frame                       */
+    int32_t* n_support;        /* i32 [M, Kp]                                                                 */
+    int32_t* best;             /* i32 [M, Kp], the winning seed; -2: none                                     */
+    int32_t* iters;            /* i32 [M, Kp], the steps the winner took                                      */
+    int32_t* flags;            /* i32 [M, Kp], SLHIP_VOTE3D_* flag bits                                       */
+    float* mean;               /* f32 [M, Kp, 3], the mean of the winner's supporters                         */
+    float* cov;                /* f32 [M, Kp, 6], their covariance (xx, xy, xz, yy, yz, zz)                   */
+    uint32_t* support;         /* u32 [M, Kp, ceil(K / 32)], bit j & 31 of word j >> 5                        */
+} slhip_keypoint_vote3d_out;
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_keypoint_vote3d_check_params(const slhip_keypoint_vote3d_params* params);
+/* d_camera f32 [M, K, 4] (x, y, z, w), 16-byte aligned: the `camera` of slhip_object_points_gather.  d_offsets f32
+ * [M, K, Kp, 3], 4-byte aligned.  Every output named in params->outputs is written for every (set, keypoint), the others are
+ * not touched.  n_sets == 0 does nothing; null pointers (an output named in the mask included), misalignment and bad
+ * parameters are refused before anything touches the device.  One workgroup per (set, keypoint).  Asynchronous on `stream`. */
+int slhip_keypoint_vote3d(const slhip_keypoint_vote3d_params* params, const float* d_camera, const float* d_offsets,
+                          const slhip_keypoint_vote3d_out* out, void* stream);
+/* The same rules on host arrays through csrc/slhip_vote3d_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_keypoint_vote3d_host(const slhip_keypoint_vote3d_params* params, const float* h_camera, const float* h_offsets,
+                               const slhip_keypoint_vote3d_out* out);
+/* Developer hook (tools/time_keypoint_vote3d.py): HIP events round the last slhip_keypoint_vote3d [0] (-1: not run). */
+int slhip_keypoint_vote3d_timing_enable(int on);
+int slhip_keypoint_vote3d_timings(float ms_out[1]);
+
+/* ---------------------------------------------------------------------------------------------
+ * Rigid fit: the pose (object to camera) of every set of N 3D-3D correspondences in the least-squares
+ * sense, by Horn's unit-quaternion form -- bank keypoints onto voted keypoints (the PVN3D pose), or
+ * predicted object coordinates onto camera points (the depth counterpart of slhip_pose_pnp).  This
+ * project's addition.  All float32, one rounded IEEE operation at a time, only + - * / sqrt fabs and
+ * comparisons; csrc/slhip_fit_rules.h holds the rules for host and device, so slhip_pose_fit_host gives
+ * the device's outputs bit for bit.  Per set:
+ *   1. correspondence j counts when src.w > 0 and dst.w != 0 and the six coordinates are finite; n_used of
+ *      them; fewer than 3: SLHIP_FIT_INSUFFICIENT.
+ *   2. centroids cs, cd = sum / (float)n_used; then the nine sums M[3 i + j] of (src_i - cs_i) * (dst_j -
+ *      cd_j).  Every sum in the order of the pose errors' means: lane j % 256 takes its correspondences
+ *      upwards from 0.0f, the butterfly in a wave, ((w0 + w1) + w2) + w3.
+ *   3. Horn's symmetric matrix in quaternion order (w, x, y, z): diagonal (Sxx + Syy) + Szz, (Sxx - Syy) -
+ *      Szz, (Syy - Sxx) - Szz, (Szz - Sxx) - Syy; N01 = Syz - Szy, N02 = Szx - Sxz, N03 = Sxy - Syx, N12 = Sxy
+ *      + Syx, N13 = Szx + Sxz, N23 = Syz + Szy.  Then 8 cyclic Jacobi sweeps over the pairs (0,1) (0,2) (0,3)
+ *      (1,2) (1,3) (2,3): a pair whose off-diagonal is exactly 0 is skipped; theta = (aqq - app) / (2 apq),
+ *      t = sign(theta) / (fabsf(theta) + sqrtf(theta*theta + 1)) with sign(0) = +1, c = 1 / sqrtf(t*t + 1),
+ *      s = t*c; app -= t*apq, aqq += t*apq, apq = 0; for the other k: akp' = c*akp - s*akq, akq' = s*akp +
+ *      c*akq; the eigenvector columns likewise.
+ *   4. the quaternion is the column of the largest diagonal entry (ties to the lowest column), divided by
+ *      its length sqrtf(((q0*q0 + q1*q1) + q2*q2) + q3*q3), negated when w < 0.
+ *   5. R = (1 - 2(yy + zz), 2(xy - wz), 2(xz + wy); 2(xy + wz), 1 - 2(xx + zz), 2(yz - wx); 2(xz - wy),
+ *      2(yz + wx), 1 - 2(xx + yy)) and t_i = cd_i - ((R_i0*cs.x + R_i1*cs.y) + R_i2*cs.z): a proper rotation
+ *      always, flat point sets included -- there is no reflection branch.
+ *   6. when the two largest eigenvalues differ by no more than min_gap * the sum of the four absolute
+ *      eigenvalues (collinear or coincident points): SLHIP_FIT_DEGENERATE.
+ *   7. rms = sqrtf(sum(|R src + t - dst|^2) / (float)n_used), each row ((R_i0*x + R_i1*y) + R_i2*z) + t_i,
+ *      the sum in the order of rule 2.
+ * INSUFFICIENT and DEGENERATE give a NaN pose and rms -- never an identity; n_used is the count in
+ * every case.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_FIT_POINTS_MAX   4096u
+#define SLHIP_FIT_OUT_POSE     1u
+#define SLHIP_FIT_OUT_N_USED   2u
+#define SLHIP_FIT_OUT_RMS      4u
+#define SLHIP_FIT_OUT_FLAGS    8u
+#define SLHIP_FIT_INSUFFICIENT 1     /* flags: fewer than 3 correspondences count                               */
+#define SLHIP_FIT_DEGENERATE   2     /* flags: collinear or coincident points                                   */
+
+typedef struct {
+    uint32_t n_sets;           /* M                                                                           */
+    uint32_t n_points;         /* N correspondences per set, 1..SLHIP_FIT_POINTS_MAX                          */
+    float min_gap;             /* in [0, 1): rule 6                                                           */
+    uint32_t outputs;          /* SLHIP_FIT_OUT_* bits, at least one                                          */
+    uint32_t _pad[12];
+} slhip_pose_fit_params; /* 64 bytes */
+
+typedef struct {               /* read only when its bit is set; every pointer 4-byte aligned                 */
+    float* pose;               /* f32 [M, 3, 4], object to camera                                             */
+    int32_t* n_used;           /* i32 [M]                                                                     */
+    float* rms;                /* f32 [M], in the unit of the points                                          */
+    int32_t* flags;            /* i32 [M], SLHIP_FIT_* flag bits                                              */
+} slhip_pose_fit_out;
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_pose_fit_check_params(const slhip_pose_fit_params* params);
+/* d_src f32 [M, N, 4] object frame, d_dst f32 [M, N, 4] camera frame, both 16-byte aligned.  Every output named in
+ * params->outputs is written for every set, the others are not touched.  n_sets == 0 does nothing; null pointers,
+ * misalignment and bad parameters are refused before anything touches the device.  One workgroup per set.  Asynchronous
+ * on `stream`.                                                                                                           */
+int slhip_pose_fit(const slhip_pose_fit_params* params, const float* d_src, const float* d_dst, const slhip_pose_fit_out* out,
+                   void* stream);
+/* The same rules on host arrays through csrc/slhip_fit_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_pose_fit_host(const slhip_pose_fit_params* params, const float* h_src, const float* h_dst, const slhip_pose_fit_out* out);
+/* Developer hook: HIP events round the last slhip_pose_fit [0] (-1: not run). */
+int slhip_pose_fit_timing_enable(int on);
+int slhip_pose_fit_timings(float ms_out[1]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).

@@ -15,6 +15,8 @@ from stillleben_amd import ObjectMasks  # noqa: F401  (additive: per-object mask
 from stillleben_amd import bop  # noqa: F401  (additive: BOP entries of a SceneBatch's views)
 from stillleben_amd import pose_pnp, PosePnP  # noqa: F401  (additive: the pose of every set of 2D-3D correspondences)
 from stillleben_amd import keypoint_vote, KeypointVotes  # noqa: F401  (additive: predicted vector fields to 2D keypoints)
+from stillleben_amd import keypoint_vote3d, KeypointVotes3D  # noqa: F401  (additive: predicted 3D offsets to camera-frame keypoints)
+from stillleben_amd import pose_fit, PoseFit  # noqa: F401  (additive: the pose of every set of 3D-3D correspondences)
 
 __all__ = _impl.__all__
 for _name in ("camera_model", "diff", "extension", "losses", "profiling"):

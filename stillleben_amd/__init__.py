@@ -42,6 +42,10 @@ from . import pose_pnp  # noqa: F401  (additive: the pose of every set of 2D-3D 
 from .pose_pnp import PosePnP  # noqa: F401
 from . import keypoint_vote  # noqa: F401  (additive: predicted vector fields to 2D keypoints by RANSAC voting, PVNet's layer)
 from .keypoint_vote import KeypointVotes  # noqa: F401
+from . import keypoint_vote3d  # noqa: F401  (additive: predicted 3D offsets to camera-frame keypoints by mean shift, PVN3D's decoder)
+from .keypoint_vote3d import KeypointVotes3D  # noqa: F401
+from . import pose_fit  # noqa: F401  (additive: the pose of every set of 3D-3D correspondences, Horn's closed form)
+from .pose_fit import PoseFit  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -54,6 +58,8 @@ __all__ = [
     'pose_vsd', 'SurfaceBank', 'PoseVSD',
     'pose_pnp', 'PosePnP',
     'keypoint_vote', 'KeypointVotes',
+    'keypoint_vote3d', 'KeypointVotes3D',
+    'pose_fit', 'PoseFit',
 ]
 
 

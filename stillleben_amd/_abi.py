@@ -61,6 +61,13 @@ PNP_INSUFFICIENT, PNP_NO_MODEL, PNP_REFINE_STOPPED, PNP_REFINE_REJECTED = 1, 2, 
 VOTE_POINTS_MAX, VOTE_HYPOTHESES_MAX = 4096, 1024                            # SLHIP_VOTE_*_MAX
 VOTE_OUT_UV, VOTE_OUT_N_INLIERS, VOTE_OUT_BEST, VOTE_OUT_FLAGS, VOTE_OUT_MEAN, VOTE_OUT_COV, VOTE_OUT_INLIERS = 1, 2, 4, 8, 16, 32, 64      # SLHIP_VOTE_OUT_*
 VOTE_INSUFFICIENT, VOTE_NO_MODEL, VOTE_REFINE_STOPPED, VOTE_REFINE_REJECTED = 1, 2, 4, 8      # SLHIP_VOTE_*: the flag bits of a (set, keypoint)
+VOTE3D_POINTS_MAX, VOTE3D_SEEDS_MAX, VOTE3D_ITERS_MAX = 4096, 1024, 64           # SLHIP_VOTE3D_*_MAX
+(VOTE3D_OUT_XYZ, VOTE3D_OUT_N_SUPPORT, VOTE3D_OUT_BEST, VOTE3D_OUT_ITERS, VOTE3D_OUT_FLAGS, VOTE3D_OUT_MEAN, VOTE3D_OUT_COV,
+ VOTE3D_OUT_SUPPORT) = 1, 2, 4, 8, 16, 32, 64, 128                               # SLHIP_VOTE3D_OUT_*
+VOTE3D_INSUFFICIENT, VOTE3D_NO_MODEL, VOTE3D_NOT_CONVERGED = 1, 2, 4             # SLHIP_VOTE3D_*: the flag bits of a (set, keypoint)
+FIT_POINTS_MAX = 4096                                                            # SLHIP_FIT_POINTS_MAX
+FIT_OUT_POSE, FIT_OUT_N_USED, FIT_OUT_RMS, FIT_OUT_FLAGS = 1, 2, 4, 8            # SLHIP_FIT_OUT_*
+FIT_INSUFFICIENT, FIT_DEGENERATE = 1, 2                                          # SLHIP_FIT_*: the flag bits of a set
 REGIONS_MAX, REGION_NONE = 255, 255                                   # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
 REGIONS_OUT_LOCAL, REGIONS_OUT_HISTOGRAM = 1, 2                        # SLHIP_REGIONS_OUT_*
 ABI_VERSION = 5
@@ -373,6 +380,34 @@ class KeypointVoteOut(C.Structure):
                 ("cov", C.c_void_p), ("inliers", C.c_void_p)]
 
 
+# slhip_keypoint_vote3d_params (include/slhip.h), 64 bytes
+KEYPOINT_VOTE3D_PARAMS_DTYPE = np.dtype([
+    ("n_sets", np.uint32), ("n_points", np.uint32), ("n_keypoints", np.uint32), ("n_seeds", np.uint32), ("bandwidth", np.float32),
+    ("max_iters", np.uint32), ("tol", np.float32), ("min_support", np.uint32), ("outputs", np.uint32), ("_pad", np.uint32, (7,)),
+])
+assert KEYPOINT_VOTE3D_PARAMS_DTYPE.itemsize == 64
+
+
+class KeypointVote3dOut(C.Structure):
+    """slhip_keypoint_vote3d_out: the output pointers of slhip_keypoint_vote3d."""
+
+    _fields_ = [("xyz", C.c_void_p), ("n_support", C.c_void_p), ("best", C.c_void_p), ("iters", C.c_void_p), ("flags", C.c_void_p),
+                ("mean", C.c_void_p), ("cov", C.c_void_p), ("support", C.c_void_p)]
+
+
+# slhip_pose_fit_params (include/slhip.h), 64 bytes
+POSE_FIT_PARAMS_DTYPE = np.dtype([
+    ("n_sets", np.uint32), ("n_points", np.uint32), ("min_gap", np.float32), ("outputs", np.uint32), ("_pad", np.uint32, (12,)),
+])
+assert POSE_FIT_PARAMS_DTYPE.itemsize == 64
+
+
+class PoseFitOut(C.Structure):
+    """slhip_pose_fit_out: the output pointers of slhip_pose_fit."""
+
+    _fields_ = [("pose", C.c_void_p), ("n_used", C.c_void_p), ("rms", C.c_void_p), ("flags", C.c_void_p)]
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -626,6 +661,18 @@ def lib():
         L.slhip_keypoint_vote_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(KeypointVoteOut)]
         L.slhip_keypoint_vote_timing_enable.argtypes = [C.c_int]
         L.slhip_keypoint_vote_timings.argtypes = [C.POINTER(C.c_float * 2)]
+    if hasattr(L, "slhip_keypoint_vote3d"):          # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_keypoint_vote3d_check_params.argtypes = [C.c_void_p]
+        L.slhip_keypoint_vote3d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(KeypointVote3dOut), C.c_void_p]
+        L.slhip_keypoint_vote3d_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(KeypointVote3dOut)]
+        L.slhip_keypoint_vote3d_timing_enable.argtypes = [C.c_int]
+        L.slhip_keypoint_vote3d_timings.argtypes = [C.POINTER(C.c_float * 1)]
+    if hasattr(L, "slhip_pose_fit"):                 # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_pose_fit_check_params.argtypes = [C.c_void_p]
+        L.slhip_pose_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseFitOut), C.c_void_p]
+        L.slhip_pose_fit_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseFitOut)]
+        L.slhip_pose_fit_timing_enable.argtypes = [C.c_int]
+        L.slhip_pose_fit_timings.argtypes = [C.POINTER(C.c_float * 1)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

@@ -604,6 +604,41 @@ class SceneBatch:
             out.classes = asset[points.scene_global.long(), (points.slot - 1).long()]
         return out
 
+    def keypoint_votes3d(self, points, offsets, **kw):
+        """sl.keypoint_vote3d.vote on the point sets of a render (`points` = what points(...) returned, with its `camera`
+        output) and predicted offsets float32 [n, K, Kp, 3] in the layout of ObjectKeypoints.offsets: a KeypointVotes3D with one
+        camera-frame position per (set, keypoint).  The result carries the class of every set's object from the batch's object
+        records, so pose_fit(votes3, bank=bank) has what it needs.  `kw`: n_seeds, bandwidth, max_iters, tol, min_support,
+        outputs."""
+        from . import keypoint_vote3d
+
+        if "classes" in kw:
+            raise TypeError("SceneBatch.keypoint_votes3d sets `classes` itself")
+        if getattr(points, "camera", None) is None:
+            raise RuntimeError("keypoint_vote3d: the ObjectPoints need their `camera` output")
+        out = keypoint_vote3d.vote(points, offsets, **kw)
+        if points.scene_global is not None:
+            nb = self.n_scenes * self.n_objects * _abi.SYNTH_OBJECT_DTYPE.itemsize
+            asset = self.d_objects[:nb].view(torch.int32).view(self.n_scenes, self.n_objects, -1)[..., 0]
+            out.classes = asset[points.scene_global.long(), (points.slot - 1).long()]
+        return out
+
+    def pose_fit(self, src, dst=None, bank=None, **kw):
+        """sl.pose_fit.solve: a PoseFit with one pose (object to camera) per set.  Either a pair of float32 [n, N, 4] tensors --
+        pose_fit(points.coord, points.camera) fits predicted or rendered object coordinates to the camera points -- or a
+        KeypointVotes3D with `bank=` (a KeypointBank or a float32 [A, Kp, 4] tensor): the bank's keypoints of every set's class
+        onto the voted ones, the PVN3D pose.  `kw`: min_gap, outputs.  pose_fit(...).dense(B, O, points.scene_global,
+        points.slot) is the [B, O, 3, 4] that pose_errors and pose_vsd take."""
+        from . import keypoint_vote3d, pose_fit
+
+        if isinstance(src, keypoint_vote3d.KeypointVotes3D):
+            if dst is not None or bank is None:
+                raise TypeError("SceneBatch.pose_fit takes a KeypointVotes3D with `bank=` and without `dst`")
+            src, dst = src.correspondences(bank)
+        elif bank is not None or dst is None:
+            raise TypeError("SceneBatch.pose_fit takes either (src, dst) tensors or a KeypointVotes3D with `bank=`")
+        return pose_fit.solve(src, dst, **kw)
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

@@ -1614,6 +1614,93 @@ int slhip_pose_fit_host(const slhip_pose_fit_params* params, const float* h_src,
 int slhip_pose_fit_timing_enable(int on);
 int slhip_pose_fit_timings(float ms_out[1]);
 
+/* ---------------------------------------------------------------------------------------------
+ * ICP: the pose (object to camera) of every set of K camera points refined against the points of its
+ * class in a slhip_pose_bank, point to point, from an initial pose -- the refinement step of DenseFusion,
+ * PVN3D, FFB6D, PoseCNN+ICP and the BOP baselines.  This project's addition.  The loop round two rules
+ * that exist: the nearest-neighbour walk of the pose errors' ADD-S and the rigid fit.  All float32, one
+ * rounded IEEE operation at a time; csrc/slhip_icp_rules.h holds the rules for host and device, so
+ * slhip_pose_icp_host gives the device's outputs bit for bit.  Per set i, class c = classes[i]:
+ *   1. the set can start when 0 <= c < n_assets and 1 <= count[c] <= n_points of the bank (else
+ *      SLHIP_ICP_BAD_CLASS) and the 12 entries of init[i] are finite (else SLHIP_ICP_NO_INIT).  A set that
+ *      cannot start has a NaN pose and rms, iters 0, n_pairs 0 and nearest -1 throughout.
+ *   2. camera point j counts when its w != 0 and x, y, z are finite.
+ *   3. into the object frame with the current pose (R, t):  d = c - t per component,
+ *      q_k = (R[0][k]*d0 + R[1][k]*d1) + R[2][k]*d2  (R transposed).  The bank is never transformed.
+ *   4. the nearest bank point: m scans [0, count[c]) upwards from (best = +inf, no index); point m replaces
+ *      the best when dist2(q, p_m) < best, dist2 = (dx*dx + dy*dy) + dz*dz of the pose errors -- the
+ *      smallest distance, among equals the lowest index.  A distance of NaN or +inf never wins; rows past
+ *      count[c] are never read.
+ *   5. the pair (j, m) counts when the point counts, an index won and best <= gate * gate (+inf passes, NaN
+ *      fails).  gate_0 = max_dist; after every fit gate = max(gate * dist_scale, min_dist).  n_pairs of
+ *      them; nearest[j] = m, or -1 without a pair.  Fewer than min_pairs: SLHIP_ICP_INSUFFICIENT.
+ *   6. the rigid fit of the pairs, src = the bank point, dst = the camera point, by rules 2 to 6 of "Rigid
+ *      fit" unchanged (centroids, moments, Horn, 8 Jacobi sweeps, quaternion, min_gap); lane j % 256
+ *      takes its pairs upwards, the butterfly in a wave, ((w0 + w1) + w2) + w3.  The result is the new
+ *      absolute pose -- poses are never composed, every iterate is a proper rotation.  A degenerate fit:
+ *      SLHIP_ICP_DEGENERATE.
+ *   7. rms = sqrtf(sum(|R src + t - dst|^2) / (float)n_pairs) of the new pose over the pairs of the fit, the
+ *      sum in the order of rule 6.
+ *   8. the loop ends when every |R_new - R_old| entry <= tol_rot and every |t_new - t_old| entry <= tol_trans
+ *      (SLHIP_ICP_CONVERGED, not a failure), or after max_iters fits.  iters = the fits done.
+ * INSUFFICIENT and DEGENERATE end the loop with a NaN pose and rms -- never an identity, never the init;
+ * n_pairs and nearest are those of the last association in every case.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_ICP_POINTS_MAX    4096u
+#define SLHIP_ICP_ITERS_MAX     64u
+#define SLHIP_ICP_OUT_POSE      1u
+#define SLHIP_ICP_OUT_N_PAIRS   2u
+#define SLHIP_ICP_OUT_RMS       4u
+#define SLHIP_ICP_OUT_ITERS     8u
+#define SLHIP_ICP_OUT_FLAGS     16u
+#define SLHIP_ICP_OUT_NEAREST   32u
+#define SLHIP_ICP_BAD_CLASS     1     /* flags: the class lies outside the bank or has no points                 */
+#define SLHIP_ICP_NO_INIT       2     /* flags: the initial pose is not finite                                   */
+#define SLHIP_ICP_INSUFFICIENT  4     /* flags: fewer than min_pairs pairs                                       */
+#define SLHIP_ICP_DEGENERATE    8     /* flags: the pairs' bank points are collinear or coincident               */
+#define SLHIP_ICP_CONVERGED     16    /* flags: the pose moved by no more than the tolerances (not a failure)    */
+#define SLHIP_ICP_FAILED        15    /* the failure bits                                                        */
+
+typedef struct {
+    uint32_t n_sets;           /* M                                                                           */
+    uint32_t n_points;         /* K camera points per set, 1..SLHIP_ICP_POINTS_MAX                            */
+    uint32_t max_iters;        /* 1..SLHIP_ICP_ITERS_MAX fits                                                 */
+    uint32_t min_pairs;        /* >= 3                                                                        */
+    float max_dist;            /* >= 0, +inf: no gate; rule 5                                                 */
+    float dist_scale;          /* in (0, 1]                                                                   */
+    float min_dist;            /* >= 0                                                                        */
+    float min_gap;             /* in [0, 1): rule 6 of "Rigid fit"                                            */
+    float tol_rot;             /* >= 0                                                                        */
+    float tol_trans;           /* >= 0                                                                        */
+    uint32_t outputs;          /* SLHIP_ICP_OUT_* bits, at least one                                          */
+    uint32_t _pad[5];
+} slhip_pose_icp_params; /* 64 bytes */
+
+typedef struct {               /* read only when its bit is set; every pointer 4-byte aligned                 */
+    float* pose;               /* f32 [M, 3, 4], object to camera                                             */
+    int32_t* n_pairs;          /* i32 [M]                                                                     */
+    float* rms;                /* f32 [M], in the unit of the points                                          */
+    int32_t* iters;            /* i32 [M]                                                                     */
+    int32_t* flags;            /* i32 [M], SLHIP_ICP_* flag bits                                              */
+    int32_t* nearest;          /* i32 [M, K]                                                                  */
+} slhip_pose_icp_out;
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_pose_icp_check_params(const slhip_pose_icp_params* params);
+/* d_camera f32 [M, K, 4] (the layout of the point sets' camera output) and d_init f32 [M, 3, 4], both 16-byte aligned;
+ * d_classes i32 [M]; of the bank only points and count are read.  Every output named in params->outputs is written for
+ * every set, the others are not touched.  n_sets == 0 does nothing; null pointers, misalignment, a bank out of range and
+ * bad parameters are refused before anything touches the device.  One workgroup per set, the class's points in LDS.
+ * Asynchronous on `stream`.                                                                                              */
+int slhip_pose_icp(const slhip_pose_icp_params* params, const float* d_camera, const float* d_init, const int32_t* d_classes,
+                   const slhip_pose_bank* bank, const slhip_pose_icp_out* out, void* stream);
+/* The same rules on host arrays through csrc/slhip_icp_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_pose_icp_host(const slhip_pose_icp_params* params, const float* h_camera, const float* h_init, const int32_t* h_classes,
+                        const slhip_pose_bank* h_bank, const slhip_pose_icp_out* out);
+/* Developer hook (tools/time_pose_icp.py): HIP events round the last slhip_pose_icp [0] (-1: not run). */
+int slhip_pose_icp_timing_enable(int on);
+int slhip_pose_icp_timings(float ms_out[1]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).

@@ -46,6 +46,8 @@ from . import keypoint_vote3d  # noqa: F401  (additive: predicted 3D offsets to 
 from .keypoint_vote3d import KeypointVotes3D  # noqa: F401
 from . import pose_fit  # noqa: F401  (additive: the pose of every set of 3D-3D correspondences, Horn's closed form)
 from .pose_fit import PoseFit  # noqa: F401
+from . import pose_icp  # noqa: F401  (additive: ICP refinement of a pose against the depth's camera points, on a model bank)
+from .pose_icp import PoseICP  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -60,6 +62,7 @@ __all__ = [
     'keypoint_vote', 'KeypointVotes',
     'keypoint_vote3d', 'KeypointVotes3D',
     'pose_fit', 'PoseFit',
+    'pose_icp', 'PoseICP',
 ]
 
 

@@ -68,6 +68,10 @@ VOTE3D_INSUFFICIENT, VOTE3D_NO_MODEL, VOTE3D_NOT_CONVERGED = 1, 2, 4            
 FIT_POINTS_MAX = 4096                                                            # SLHIP_FIT_POINTS_MAX
 FIT_OUT_POSE, FIT_OUT_N_USED, FIT_OUT_RMS, FIT_OUT_FLAGS = 1, 2, 4, 8            # SLHIP_FIT_OUT_*
 FIT_INSUFFICIENT, FIT_DEGENERATE = 1, 2                                          # SLHIP_FIT_*: the flag bits of a set
+ICP_POINTS_MAX, ICP_ITERS_MAX = 4096, 64                                         # SLHIP_ICP_POINTS_MAX, SLHIP_ICP_ITERS_MAX
+ICP_OUT_POSE, ICP_OUT_N_PAIRS, ICP_OUT_RMS, ICP_OUT_ITERS, ICP_OUT_FLAGS, ICP_OUT_NEAREST = 1, 2, 4, 8, 16, 32      # SLHIP_ICP_OUT_*
+ICP_BAD_CLASS, ICP_NO_INIT, ICP_INSUFFICIENT, ICP_DEGENERATE, ICP_CONVERGED = 1, 2, 4, 8, 16      # SLHIP_ICP_*: the flag bits of a set
+ICP_FAILED = 15                                                                  # SLHIP_ICP_FAILED: the failure bits
 REGIONS_MAX, REGION_NONE = 255, 255                                   # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
 REGIONS_OUT_LOCAL, REGIONS_OUT_HISTOGRAM = 1, 2                        # SLHIP_REGIONS_OUT_*
 ABI_VERSION = 5
@@ -408,6 +412,22 @@ class PoseFitOut(C.Structure):
     _fields_ = [("pose", C.c_void_p), ("n_used", C.c_void_p), ("rms", C.c_void_p), ("flags", C.c_void_p)]
 
 
+# slhip_pose_icp_params (include/slhip.h), 64 bytes
+POSE_ICP_PARAMS_DTYPE = np.dtype([
+    ("n_sets", np.uint32), ("n_points", np.uint32), ("max_iters", np.uint32), ("min_pairs", np.uint32), ("max_dist", np.float32),
+    ("dist_scale", np.float32), ("min_dist", np.float32), ("min_gap", np.float32), ("tol_rot", np.float32), ("tol_trans", np.float32),
+    ("outputs", np.uint32), ("_pad", np.uint32, (5,)),
+])
+assert POSE_ICP_PARAMS_DTYPE.itemsize == 64
+
+
+class PoseIcpOut(C.Structure):
+    """slhip_pose_icp_out: the output pointers of slhip_pose_icp."""
+
+    _fields_ = [("pose", C.c_void_p), ("n_pairs", C.c_void_p), ("rms", C.c_void_p), ("iters", C.c_void_p), ("flags", C.c_void_p),
+                ("nearest", C.c_void_p)]
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -673,6 +693,12 @@ def lib():
         L.slhip_pose_fit_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseFitOut)]
         L.slhip_pose_fit_timing_enable.argtypes = [C.c_int]
         L.slhip_pose_fit_timings.argtypes = [C.POINTER(C.c_float * 1)]
+    if hasattr(L, "slhip_pose_icp"):                 # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_pose_icp_check_params.argtypes = [C.c_void_p]
+        L.slhip_pose_icp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseBank), C.POINTER(PoseIcpOut), C.c_void_p]
+        L.slhip_pose_icp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseBank), C.POINTER(PoseIcpOut)]
+        L.slhip_pose_icp_timing_enable.argtypes = [C.c_int]
+        L.slhip_pose_icp_timings.argtypes = [C.POINTER(C.c_float * 1)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

@@ -639,6 +639,37 @@ class SceneBatch:
             raise TypeError("SceneBatch.pose_fit takes either (src, dst) tensors or a KeypointVotes3D with `bank=`")
         return pose_fit.solve(src, dst, **kw)
 
+    def pose_icp(self, points, init, bank, **kw):
+        """sl.pose_icp.solve on the point sets of a render (`points` = what points(...) returned, with its `camera` output): a
+        PoseICP with one refined pose (object to camera) per set.  `init`: the initial poses as float32 [n, 3, 4], a PoseFit or
+        PosePnP (its `.pose`), or float32 [B, O, 3, 4] for all scenes of the batch, gathered by points.scene_global and
+        points.slot.  `bank`: a ModelBank of the batch's table (sl.pose_error.bank(table, ...); surface-sampled points from
+        sl.pose_icp.surface_points serve low-poly classes).  The class of every set's object comes from the batch's object
+        records.  `kw`: max_iters, max_dist, dist_scale, min_dist, min_pairs, min_gap, tol_rot, tol_trans, outputs.
+        pose_icp(...).dense(B, O, points.scene_global, points.slot) is the [B, O, 3, 4] that pose_errors and pose_vsd take."""
+        from . import _device, pose_icp
+
+        if "classes" in kw:
+            raise TypeError("SceneBatch.pose_icp sets `classes` itself")
+        if getattr(points, "camera", None) is None:
+            raise RuntimeError("pose_icp: the ObjectPoints need their `camera` output")
+        if points.scene_global is None:
+            raise RuntimeError("pose_icp: the ObjectPoints carry no scene_global (they do not come from this batch's points())")
+        if not isinstance(init, torch.Tensor):
+            init = getattr(init, "pose", None)
+            if init is None:
+                raise TypeError("SceneBatch.pose_icp: `init` must be a tensor, or a PoseFit / PosePnP with its `pose` output")
+        scene, slot = points.scene_global.long(), (points.slot - 1).long()
+        if init.dim() == 4:
+            if not init.is_cuda:
+                raise _abi.SlhipError(_device.no_cpu("pose_icp"))
+            init = init[scene, slot]
+        nb = self.n_scenes * self.n_objects * _abi.SYNTH_OBJECT_DTYPE.itemsize
+        asset = self.d_objects[:nb].view(torch.int32).view(self.n_scenes, self.n_objects, -1)[..., 0]
+        if not init.is_cuda or not points.camera.is_cuda:
+            raise _abi.SlhipError(_device.no_cpu("pose_icp"))
+        return pose_icp.solve(points.camera, init.contiguous(), asset[scene, slot].contiguous(), bank, **kw)
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()

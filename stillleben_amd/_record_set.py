@@ -1,7 +1,10 @@
 """What sl.object_crops and sl.object_points share: the record-set class behind ObjectCrops and ObjectPoints and the select step
-of their extract() -- statistics (and mask records) to a compact array of records in ascending (scene, slot) order."""
+of their extract() -- statistics (and mask records) to a compact array of records in ascending (scene, slot) order.  And what the
+pose family shares (pose_fit, pose_icp, pose_pnp, keypoint_vote, keypoint_vote3d): OutputSet, the class behind their results,
+which derives the outputs' names, arrays and ctypes record from one table per module."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _abi, _device
@@ -93,3 +96,99 @@ def select(entry, rec, inputs, B, S, extra, words, dev):
 def empty_outputs(n, bits, dev, spec):
     """{name: a tensor [n, *shape] for every (name, bit, shape, dtype) of `spec` whose bit is in `bits`, None for the others}"""
     return {name: torch.empty((n,) + shape, dtype=dtype, device=dev) if bits & bit else None for name, bit, shape, dtype in spec}
+
+
+def n_words(K):
+    """The 32-bit words of K bits."""
+    return (int(K) + 31) // 32
+
+
+def bit_mask(words, K):
+    """bool [..., K] of uint32 words [..., n_words(K)] (numpy, or int32 on the device): bit j & 31 of word j >> 5."""
+    if isinstance(words, np.ndarray):
+        j = np.arange(K)
+        return ((words.view(np.uint32)[..., j >> 5] >> (j & 31).astype(np.uint32)) & 1).astype(bool)
+    j = torch.arange(K, device=words.device)
+    return ((words[..., j >> 5] >> (j & 31).to(torch.int32)) & 1).bool()
+
+
+_TORCH = {np.float32: torch.float32, np.int32: torch.int32, np.uint32: torch.int32}      # (bit words are int32 on the device)
+
+
+class OutputSet:
+    """The result of a pose-family module (pose_fit, pose_icp, pose_pnp, keypoint_vote, keypoint_vote3d): one optional array per
+    output, torch tensors on the device or numpy arrays from the host twin; those not asked for are None.  A subclass states
+        NAME    its module, for messages
+        TABLE   ((name, bit of `outputs`, shape of one item, numpy dtype), ...) in the field order of RECORD; a dimension is a
+                number or the name of a size that `empty` is given.  The first row is the result itself, NaN for an item without one
+        RECORD  the ctypes record of the output pointers (_abi)
+        FAILED  the bits of `flags` that leave an item without a result
+    and gets OUTPUTS = {name: bit} from the table."""
+    NAME, TABLE, RECORD, FAILED = "", (), None, 0
+
+    def __init_subclass__(cls):
+        if cls.RECORD is not None:
+            assert [row[0] for row in cls.TABLE] == [f[0] for f in cls.RECORD._fields_], cls.NAME
+        cls.OUTPUTS = {name: bit for name, bit, _, _ in cls.TABLE}
+
+    def __init__(self, **outs):
+        for name in self.OUTPUTS:
+            setattr(self, name, outs.pop(name, None))
+        if outs:
+            raise TypeError("%s: unknown output %r" % (self.NAME, sorted(outs)[0]))
+        self._keepalive = ()
+
+    @classmethod
+    def empty(cls, lead, bits, dev=None, **sizes):
+        """{name: an array [*lead, *item shape] for every output of TABLE in `bits`}: numpy zeros, or torch tensors on `dev`."""
+        outs = {}
+        for name, bit, shape, dtype in cls.TABLE:
+            if bits & bit:
+                full = tuple(lead) + tuple(sizes[d] if isinstance(d, str) else d for d in shape)
+                outs[name] = np.zeros(full, dtype) if dev is None else torch.empty(full, dtype=_TORCH[dtype], device=dev)
+        return outs
+
+    def record(self):
+        """The ctypes record of the arrays' addresses, null for an output that is None."""
+        def address(a):
+            return None if a is None else a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+        return self.RECORD(*(address(getattr(self, name)) for name in self.OUTPUTS))
+
+    def __len__(self):
+        for name in self.OUTPUTS:
+            if getattr(self, name) is not None:
+                return int(getattr(self, name).shape[0])
+        return 0
+
+    @property
+    def found(self):
+        """bool, one per item: it has a result.  Read from `flags` (no bit of FAILED), without them from `best` (-2: none),
+        without both from the result itself (NaN: none)."""
+        if self.flags is not None:
+            return (self.flags & self.FAILED) == 0
+        if getattr(self, "best", None) is not None:
+            return self.best != -2
+        name, _, shape, _ = self.TABLE[0]
+        value = getattr(self, name)
+        if value is None:
+            reads = ", ".join("`%s`" % n for n in ("flags", "best", name) if n in self.OUTPUTS)
+            raise RuntimeError("%s: `found` reads one of the outputs %s, and none of them was asked for" % (self.NAME, reads))
+        first = value[(Ellipsis,) + (0,) * len(shape)]
+        return first == first
+
+
+class PoseSet(OutputSet):
+    """An OutputSet with one `pose` float32 [M, 3, 4] per set."""
+
+    def dense(self, B, O, scene, slot):
+        """float32 [B, O, 3, 4]: the pose of set i at [scene[i], slot[i] - 1], NaN where a (scene, slot) has no set -- the shape
+        SceneBatch.pose_errors and SceneBatch.pose_vsd take.  `slot` counts from 1 as the renders' instance indices do."""
+        if self.pose is None:
+            raise RuntimeError("%s: the `pose` output was not asked for" % self.NAME)
+        if isinstance(self.pose, np.ndarray):
+            out = np.full((int(B), int(O), 3, 4), np.nan, np.float32)
+            out[np.asarray(scene, np.int64), np.asarray(slot, np.int64) - 1] = self.pose
+            return out
+        out = torch.full((int(B), int(O), 3, 4), float("nan"), dtype=torch.float32, device=self.pose.device)
+        out[torch.as_tensor(scene, device=out.device).long(), torch.as_tensor(slot, device=out.device).long() - 1] = self.pose
+        return out

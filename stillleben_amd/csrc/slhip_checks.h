@@ -1,8 +1,10 @@
-// slhip_checks.h -- the argument checks that the per-object outputs share (slhip_object_*_check_params and their entries): one
-// place per rule and per error text.  Host code; a failed check sets the error text and returns -1.
+// slhip_checks.h -- the argument checks that the per-object outputs and the pose family share (slhip_*_check_params and their
+// entries): one place per rule and per error text.  Host code; a failed check sets the error text and returns -1.
 #pragma once
 
 #include <stdint.h>
+
+#include <initializer_list>
 
 #include "slhip_common.h"
 
@@ -43,6 +45,44 @@ inline int check_picture_sides(const char* who, int W, int H)
         set_error("%s: bad picture size %d x %d (each side 1..32768)", who, W, H);
         return -1;
     }
+    return 0;
+}
+
+// the fit's min_gap: in [0, 1), and no NaN
+inline int check_min_gap(const char* who, float min_gap)
+{
+    if (!(min_gap >= 0.0f) || !(min_gap < 1.0f)) {
+        set_error("%s: min_gap %g must lie in [0, 1)", who, (double)min_gap);
+        return -1;
+    }
+    return 0;
+}
+
+// One optional output of a module's output record: the bit of `outputs` that names it and its pointer.  The two checks below take
+// the whole record as a brace list: const slhip::OutputList outputs = {{SLHIP_X_OUT_A, out->a}, {SLHIP_X_OUT_B, out->b}, ...};
+struct NamedOutput {
+    uint32_t bit;
+    const void* ptr;
+};
+using OutputList = std::initializer_list<NamedOutput>;
+
+inline int check_outputs_present(const char* who, uint32_t outputs, OutputList all)
+{
+    for (const NamedOutput& o : all)
+        if ((outputs & o.bit) && !o.ptr) {
+            set_error("%s: an output named in `outputs` (0x%x) has a null pointer", who, outputs);
+            return -1;
+        }
+    return 0;
+}
+
+inline int check_outputs_aligned(const char* who, uint32_t outputs, OutputList all)
+{
+    for (const NamedOutput& o : all)
+        if ((outputs & o.bit) && ((uintptr_t)o.ptr & 3u)) {
+            set_error("%s: every output must be 4-byte aligned", who);
+            return -1;
+        }
     return 0;
 }
 

@@ -9,7 +9,7 @@
 //                     then the score with q in registers and the voters by 16-byte LDS reads at one address for all lanes (a
 //                     broadcast), no barrier inside a round; (qx, qy, count) of every hypothesis into LDS;  (3) arg-max of
 //                     (count, lowest index) by wave then workgroup;  (4) mean and covariance: lanes over hypotheses, two passes of
-//                     three sums in pose_error's order;  (5) the fit: lanes over the valid list, five sums, every lane solves the
+//                     three sums (slhip_block_sum.h);  (5) the fit: lanes over the valid list, five sums, every lane solves the
 //                     2 x 2;  (6) the final pass over the voters in their own order from LDS: ballot words and the count
 #include <hip/hip_runtime.h>
 
@@ -33,45 +33,16 @@ namespace vt = slhip_vote;
 
 constexpr uint32_t BLOCK = vt::BLOCK;
 constexpr uint32_t NWAVES = BLOCK / vt::WAVE;
-constexpr uint32_t SUMS = 5u;        // the most sums of one reduction (the fit's)
+constexpr int SUMS = 5;            // the most sums of one reduction (the fit's)
 constexpr uint32_t SMALL = 2u * NWAVES + NWAVES * SUMS + 2u;      // the words behind the planes: counts, keys, partial sums, q
 constexpr uint32_t N_SETS_MAX = 0x7fffffffu / SLHIP_KEYPOINTS_MAX;      // the grid is n_sets * n_keypoints blocks
 
-__host__ __device__ inline uint32_t pad4(uint32_t n) { return (n + 3u) & ~3u; }
-__host__ __device__ inline uint32_t words_of(uint32_t K) { return (K + 31u) / 32u; }
-__host__ __device__ inline uint32_t chunks_of(uint32_t K) { return (K + 63u) / 64u; }
+using slhip_pose::chunks_of;
+using slhip_pose::pad4;
+using slhip_pose::words_of;
 
 // dynamic LDS in 4-byte words: 4 voter planes, 3 hypothesis planes, a validity word pair and a first rank per 64 voters, SMALL
 __host__ __device__ inline uint32_t lds_words(uint32_t K, uint32_t Hy) { return 4u * pad4(K) + 3u * pad4(Hy) + 4u * chunks_of(K) + SMALL; }
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
-    return v;
-}
-
-// S[i] = the workgroup's sum of acc[i] in pose_error's order: the butterfly in a wave, then ((w0 + w1) + w2) + w3
-template <int N>
-__device__ __forceinline__ void block_sums(const float* acc, float* s_part, uint32_t wave, uint32_t lane, float* S)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float w = wave_sum(acc[i]);
-        if (lane == 0u) s_part[wave * SUMS + i] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) S[i] = ((s_part[i] + s_part[SUMS + i]) + s_part[2u * SUMS + i]) + s_part[3u * SUMS + i];
-    __syncthreads();      // the sums are read before the next reduction writes them
-}
 
 // INSUFFICIENT / NO_MODEL: NaN uv, mean and cov, 0 inliers, best -2, zero bits (lane 0, and the words by all lanes)
 __device__ void write_none(const Params& p, const Out& out, uint32_t o, int flags)
@@ -204,7 +175,7 @@ __global__ __launch_bounds__(BLOCK) void k_keypoint_vote(Params p, const short2*
     }
 
     // (3) the winner: highest count, then lowest h; every hypothesis has a key of its own, so one lane owns the maximum
-    const uint32_t wkey = wave_max(best_key);
+    const uint32_t wkey = slhip_pose::wave_max(best_key);
     if (lane == 0u) s_key[wave] = wkey;
     __syncthreads();
     const uint32_t win = max(max(s_key[0], s_key[1]), max(s_key[2], s_key[3]));
@@ -226,14 +197,14 @@ __global__ __launch_bounds__(BLOCK) void k_keypoint_vote(Params p, const short2*
         float acc[3] = {0.0f, 0.0f, 0.0f}, S[3];
         for (uint32_t h = tid; h < Hy; h += BLOCK)
             if (s_qx[h] == s_qx[h]) vt::accumulate_mean(vt::weight(s_count[h], n_valid), s_qx[h], s_qy[h], acc);
-        block_sums<3>(acc, s_part, wave, lane, S);
+        slhip_pose::block_sums<3, SUMS>(acc, s_part, wave, lane, S);
         const float sw = S[0];
         mean_x = S[1] / sw;
         mean_y = S[2] / sw;
         acc[0] = acc[1] = acc[2] = 0.0f;
         for (uint32_t h = tid; h < Hy; h += BLOCK)
             if (s_qx[h] == s_qx[h]) vt::accumulate_cov(vt::weight(s_count[h], n_valid), s_qx[h], s_qy[h], mean_x, mean_y, acc);
-        block_sums<3>(acc, s_part, wave, lane, S);
+        slhip_pose::block_sums<3, SUMS>(acc, s_part, wave, lane, S);
         cov[0] = S[0] / sw; cov[1] = S[1] / sw; cov[2] = S[2] / sw;
     }
 
@@ -243,7 +214,7 @@ __global__ __launch_bounds__(BLOCK) void k_keypoint_vote(Params p, const short2*
         float acc[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, S[5];
         for (uint32_t i = tid; i < n_valid; i += BLOCK)
             if (vt::inlier(qx, qy, s_px[i], s_py[i], s_dx[i], s_dy[i], cc)) vt::accumulate_fit(qx, qy, s_px[i], s_py[i], s_dx[i], s_dy[i], acc);
-        block_sums<5>(acc, s_part, wave, lane, S);
+        slhip_pose::block_sums<5, SUMS>(acc, s_part, wave, lane, S);
         if (!vt::fit(S, qx, qy, &uv)) flags |= SLHIP_VOTE_REFINE_STOPPED;      // the same for every lane
     }
 
@@ -271,7 +242,7 @@ __global__ __launch_bounds__(BLOCK) void k_keypoint_vote(Params p, const short2*
         }
         if (lane == 0u) s_cnt[wave] = mine;
         __syncthreads();
-        const uint32_t count = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
+        const uint32_t count = slhip_pose::waves_sum(s_cnt);
         __syncthreads();
         if (pass == 0 && count < win_count) {      // the same for every lane; only a refined position can get here
             flags |= SLHIP_VOTE_REFINE_REJECTED;
@@ -317,26 +288,15 @@ int check_call(const char* who, const Params* params, const int16_t* pixel, cons
         return -1;
     }
     const uint32_t m = params->outputs;
-    if (((m & SLHIP_VOTE_OUT_UV) && !out->uv) || ((m & SLHIP_VOTE_OUT_N_INLIERS) && !out->n_inliers) ||
-        ((m & SLHIP_VOTE_OUT_BEST) && !out->best) || ((m & SLHIP_VOTE_OUT_FLAGS) && !out->flags) ||
-        ((m & SLHIP_VOTE_OUT_MEAN) && !out->mean) || ((m & SLHIP_VOTE_OUT_COV) && !out->cov) ||
-        ((m & SLHIP_VOTE_OUT_INLIERS) && !out->inliers)) {
-        slhip::set_error("%s: an output named in `outputs` (0x%x) has a null pointer", who, m);
-        return -1;
-    }
+    const slhip::OutputList outputs = {{SLHIP_VOTE_OUT_UV, out->uv},       {SLHIP_VOTE_OUT_N_INLIERS, out->n_inliers}, {SLHIP_VOTE_OUT_BEST, out->best},
+                                       {SLHIP_VOTE_OUT_FLAGS, out->flags}, {SLHIP_VOTE_OUT_MEAN, out->mean},           {SLHIP_VOTE_OUT_COV, out->cov},
+                                       {SLHIP_VOTE_OUT_INLIERS, out->inliers}};
+    if (const int st = slhip::check_outputs_present(who, m, outputs)) return st;
     if (((uintptr_t)pixel & 3u) || ((uintptr_t)vectors & 7u) || ((uintptr_t)scene & 3u)) {
         slhip::set_error("%s: the pixels and the scenes must be 4-byte aligned, the vectors 8-byte", who);
         return -1;
     }
-    const uintptr_t all = ((m & SLHIP_VOTE_OUT_UV) ? (uintptr_t)out->uv : 0u) | ((m & SLHIP_VOTE_OUT_N_INLIERS) ? (uintptr_t)out->n_inliers : 0u) |
-                          ((m & SLHIP_VOTE_OUT_BEST) ? (uintptr_t)out->best : 0u) | ((m & SLHIP_VOTE_OUT_FLAGS) ? (uintptr_t)out->flags : 0u) |
-                          ((m & SLHIP_VOTE_OUT_MEAN) ? (uintptr_t)out->mean : 0u) | ((m & SLHIP_VOTE_OUT_COV) ? (uintptr_t)out->cov : 0u) |
-                          ((m & SLHIP_VOTE_OUT_INLIERS) ? (uintptr_t)out->inliers : 0u);
-    if (all & 3u) {
-        slhip::set_error("%s: every output must be 4-byte aligned", who);
-        return -1;
-    }
-    return 0;
+    return slhip::check_outputs_aligned(who, m, outputs);
 }
 
 // optional HIP-event timing (tools/time_keypoint_vote.py): events round the last whole call [0] and the last call that read a
@@ -347,14 +307,7 @@ slhip::StepTimer<2> g_timer;
 
 extern "C" int slhip_keypoint_vote_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_keypoint_vote_timings(float ms_out[2])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_keypoint_vote_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_keypoint_vote_timings(float ms_out[2]) { return g_timer.read_for("slhip_keypoint_vote_timings", ms_out); }
 
 extern "C" int slhip_keypoint_vote_check_params(const slhip_keypoint_vote_params* p)
 {
@@ -472,35 +425,23 @@ extern "C" int slhip_keypoint_vote_host(const slhip_keypoint_vote_params* params
             const int best = vt::key_best(win);
             const float qx = hyp[best].x, qy = hyp[best].y;
             int flags = 0;
-            // upwards: lane h % BLOCK (i % BLOCK) meets its items in rising order
-            float lanes[5][BLOCK] = {};
-            for (uint32_t h = 0u; h < Hy; ++h) {
-                if (!have[h]) continue;
-                float acc[3] = {lanes[0][h % BLOCK], lanes[1][h % BLOCK], lanes[2][h % BLOCK]};
-                vt::accumulate_mean(vt::weight(counts[h], n_valid), hyp[h].x, hyp[h].y, acc);
-                for (int s = 0; s < 3; ++s) lanes[s][h % BLOCK] = acc[s];
-            }
-            const float sw = slhip_pose::block_sum(lanes[0]);
-            const float mean_x = slhip_pose::block_sum(lanes[1]) / sw, mean_y = slhip_pose::block_sum(lanes[2]) / sw;
-            for (int s = 0; s < 3; ++s) std::fill(lanes[s], lanes[s] + BLOCK, 0.0f);
-            for (uint32_t h = 0u; h < Hy; ++h) {
-                if (!have[h]) continue;
-                float acc[3] = {lanes[0][h % BLOCK], lanes[1][h % BLOCK], lanes[2][h % BLOCK]};
-                vt::accumulate_cov(vt::weight(counts[h], n_valid), hyp[h].x, hyp[h].y, mean_x, mean_y, acc);
-                for (int s = 0; s < 3; ++s) lanes[s][h % BLOCK] = acc[s];
-            }
-            const float cov[3] = {slhip_pose::block_sum(lanes[0]) / sw, slhip_pose::block_sum(lanes[1]) / sw, slhip_pose::block_sum(lanes[2]) / sw};
-            for (int s = 0; s < 5; ++s) std::fill(lanes[s], lanes[s] + BLOCK, 0.0f);
+            slhip_pose::LaneSums<3> mean_sums, cov_sums;
+            for (uint32_t h = 0u; h < Hy; ++h)
+                if (have[h]) mean_sums.add(h, [&](float* acc) { vt::accumulate_mean(vt::weight(counts[h], n_valid), hyp[h].x, hyp[h].y, acc); });
+            const float sw = mean_sums.total(0);
+            const float mean_x = mean_sums.total(1) / sw, mean_y = mean_sums.total(2) / sw;
+            for (uint32_t h = 0u; h < Hy; ++h)
+                if (have[h])
+                    cov_sums.add(h, [&](float* acc) { vt::accumulate_cov(vt::weight(counts[h], n_valid), hyp[h].x, hyp[h].y, mean_x, mean_y, acc); });
+            const float cov[3] = {cov_sums.total(0) / sw, cov_sums.total(1) / sw, cov_sums.total(2) / sw};
+            slhip_pose::LaneSums<5> fit_sums;
             for (uint32_t i = 0u; i < n_valid; ++i) {
                 const vt::Voter& v = list[i];
-                if (!vt::inlier(qx, qy, v.px, v.py, v.dx, v.dy, cc)) continue;
-                float acc[5];
-                for (int s = 0; s < 5; ++s) acc[s] = lanes[s][i % BLOCK];
-                vt::accumulate_fit(qx, qy, v.px, v.py, v.dx, v.dy, acc);
-                for (int s = 0; s < 5; ++s) lanes[s][i % BLOCK] = acc[s];
+                if (vt::inlier(qx, qy, v.px, v.py, v.dx, v.dy, cc))
+                    fit_sums.add(i, [&](float* acc) { vt::accumulate_fit(qx, qy, v.px, v.py, v.dx, v.dy, acc); });
             }
             float S[5];
-            for (int s = 0; s < 5; ++s) S[s] = slhip_pose::block_sum(lanes[s]);
+            for (int s = 0; s < 5; ++s) S[s] = fit_sums.total(s);
             vt::Q uv;
             if (!vt::fit(S, qx, qy, &uv)) flags |= SLHIP_VOTE_REFINE_STOPPED;
             for (int pass = 0; pass < 2; ++pass) {

@@ -11,7 +11,7 @@
 //                      sequentially -- no barrier and no cross-lane step inside; a lane whose seed has stopped idles;  (3) arg-max
 //                      of (support, lowest seed) by wave then workgroup, the winner's lane leaves its mode in LDS;  (4) the
 //                      supporters of the mode over the voters in their own order: ballot words and the count;  (5) mean and
-//                      covariance of the supporters: lanes over the valid list, two passes in pose_error's order.
+//                      covariance of the supporters: lanes over the valid list, two passes of sums (slhip_block_sum.h).
 // Every loop is bounded by max_iters, n_seeds and K; nothing waits on another workgroup.
 #include <hip/hip_runtime.h>
 
@@ -35,46 +35,17 @@ namespace vt = slhip_vote3d;
 
 constexpr uint32_t BLOCK = vt::BLOCK;
 constexpr uint32_t NWAVES = BLOCK / vt::WAVE;
-constexpr uint32_t SUMS = 6u;        // the most sums of one reduction (the covariance's)
+constexpr int SUMS = 6;            // the most sums of one reduction (the covariance's)
 constexpr uint32_t SMALL = 2u * NWAVES + NWAVES * SUMS + 8u;      // the words behind the planes: counts, keys, partial sums, winner
 constexpr uint32_t N_SETS_MAX = 0x7fffffffu / SLHIP_KEYPOINTS_MAX;      // the grid is n_sets * n_keypoints blocks
 
-__host__ __device__ inline uint32_t pad4(uint32_t n) { return (n + 3u) & ~3u; }
-__host__ __device__ inline uint32_t words_of(uint32_t K) { return (K + 31u) / 32u; }
-__host__ __device__ inline uint32_t chunks_of(uint32_t K) { return (K + 63u) / 64u; }
+using slhip_pose::chunks_of;
+using slhip_pose::pad4;
+using slhip_pose::words_of;
 
 // dynamic LDS in 4-byte words: 3 candidate planes, a validity word pair and a first rank (and a spare) per 64 voters, SMALL:
 // 49 KiB + 1 KiB + 168 B at K = 4096, under the 64 KiB a kernel may ask for without an attribute
 __host__ __device__ inline uint32_t lds_words(uint32_t K) { return 3u * pad4(K) + 4u * chunks_of(K) + SMALL; }
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
-    return v;
-}
-
-// S[i] = the workgroup's sum of acc[i] in pose_error's order: the butterfly in a wave, then ((w0 + w1) + w2) + w3
-template <int N>
-__device__ __forceinline__ void block_sums(const float* acc, float* s_part, uint32_t wave, uint32_t lane, float* S)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float w = wave_sum(acc[i]);
-        if (lane == 0u) s_part[wave * SUMS + i] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) S[i] = ((s_part[i] + s_part[SUMS + i]) + s_part[2u * SUMS + i]) + s_part[3u * SUMS + i];
-    __syncthreads();      // the sums are read before the next reduction writes them
-}
 
 // INSUFFICIENT / NO_MODEL: NaN xyz, mean and cov, 0 supporters, best -2, 0 iterations, zero bits (lane 0, and the words by all lanes)
 __device__ void write_none(const Params& p, const Out& out, uint32_t o, int flags)
@@ -213,7 +184,7 @@ __global__ __launch_bounds__(BLOCK) void k_keypoint_vote3d(Params p, const float
     }
 
     // (3) the winner: highest support, then lowest s; every seed has a key of its own, so one lane owns the maximum
-    const uint32_t wkey = wave_max(best_key);
+    const uint32_t wkey = slhip_pose::wave_max(best_key);
     if (lane == 0u) s_key[wave] = wkey;
     __syncthreads();
     const uint32_t win = max(max(s_key[0], s_key[1]), max(s_key[2], s_key[3]));
@@ -262,12 +233,12 @@ __global__ __launch_bounds__(BLOCK) void k_keypoint_vote3d(Params p, const float
         float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, S[6];
         for (uint32_t i = tid; i < n_valid; i += BLOCK)
             if (vt::supports(mode, s_cx[i], s_cy[i], s_cz[i], h2)) vt::accumulate_mean(s_cx[i], s_cy[i], s_cz[i], acc);
-        block_sums<3>(acc, s_part, wave, lane, S);
+        slhip_pose::block_sums<3, SUMS>(acc, s_part, wave, lane, S);
         mean.x = S[0] / count; mean.y = S[1] / count; mean.z = S[2] / count;
         acc[0] = acc[1] = acc[2] = 0.0f;
         for (uint32_t i = tid; i < n_valid; i += BLOCK)
             if (vt::supports(mode, s_cx[i], s_cy[i], s_cz[i], h2)) vt::accumulate_cov(s_cx[i], s_cy[i], s_cz[i], mean, acc);
-        block_sums<6>(acc, s_part, wave, lane, S);
+        slhip_pose::block_sums<6, SUMS>(acc, s_part, wave, lane, S);
 #pragma unroll
         for (int i = 0; i < 6; ++i) cov[i] = S[i] / count;
     }
@@ -300,26 +271,15 @@ int check_call(const char* who, const Params* params, const float* camera, const
         return -1;
     }
     const uint32_t m = params->outputs;
-    if (((m & SLHIP_VOTE3D_OUT_XYZ) && !out->xyz) || ((m & SLHIP_VOTE3D_OUT_N_SUPPORT) && !out->n_support) ||
-        ((m & SLHIP_VOTE3D_OUT_BEST) && !out->best) || ((m & SLHIP_VOTE3D_OUT_ITERS) && !out->iters) ||
-        ((m & SLHIP_VOTE3D_OUT_FLAGS) && !out->flags) || ((m & SLHIP_VOTE3D_OUT_MEAN) && !out->mean) ||
-        ((m & SLHIP_VOTE3D_OUT_COV) && !out->cov) || ((m & SLHIP_VOTE3D_OUT_SUPPORT) && !out->support)) {
-        slhip::set_error("%s: an output named in `outputs` (0x%x) has a null pointer", who, m);
-        return -1;
-    }
+    const slhip::OutputList outputs = {{SLHIP_VOTE3D_OUT_XYZ, out->xyz},     {SLHIP_VOTE3D_OUT_N_SUPPORT, out->n_support}, {SLHIP_VOTE3D_OUT_BEST, out->best},
+                                       {SLHIP_VOTE3D_OUT_ITERS, out->iters}, {SLHIP_VOTE3D_OUT_FLAGS, out->flags},         {SLHIP_VOTE3D_OUT_MEAN, out->mean},
+                                       {SLHIP_VOTE3D_OUT_COV, out->cov},     {SLHIP_VOTE3D_OUT_SUPPORT, out->support}};
+    if (const int st = slhip::check_outputs_present(who, m, outputs)) return st;
     if (((uintptr_t)camera & 15u) || ((uintptr_t)offsets & 3u)) {
         slhip::set_error("%s: the camera points must be 16-byte aligned, the offsets 4-byte", who);
         return -1;
     }
-    const uintptr_t all = ((m & SLHIP_VOTE3D_OUT_XYZ) ? (uintptr_t)out->xyz : 0u) | ((m & SLHIP_VOTE3D_OUT_N_SUPPORT) ? (uintptr_t)out->n_support : 0u) |
-                          ((m & SLHIP_VOTE3D_OUT_BEST) ? (uintptr_t)out->best : 0u) | ((m & SLHIP_VOTE3D_OUT_ITERS) ? (uintptr_t)out->iters : 0u) |
-                          ((m & SLHIP_VOTE3D_OUT_FLAGS) ? (uintptr_t)out->flags : 0u) | ((m & SLHIP_VOTE3D_OUT_MEAN) ? (uintptr_t)out->mean : 0u) |
-                          ((m & SLHIP_VOTE3D_OUT_COV) ? (uintptr_t)out->cov : 0u) | ((m & SLHIP_VOTE3D_OUT_SUPPORT) ? (uintptr_t)out->support : 0u);
-    if (all & 3u) {
-        slhip::set_error("%s: every output must be 4-byte aligned", who);
-        return -1;
-    }
-    return 0;
+    return slhip::check_outputs_aligned(who, m, outputs);
 }
 
 // optional HIP-event timing (tools/time_keypoint_vote3d.py): events round the last call
@@ -329,14 +289,7 @@ slhip::StepTimer<1> g_timer;
 
 extern "C" int slhip_keypoint_vote3d_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_keypoint_vote3d_timings(float ms_out[1])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_keypoint_vote3d_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_keypoint_vote3d_timings(float ms_out[1]) { return g_timer.read_for("slhip_keypoint_vote3d_timings", ms_out); }
 
 extern "C" int slhip_keypoint_vote3d_check_params(const slhip_keypoint_vote3d_params* p)
 {
@@ -450,25 +403,16 @@ extern "C" int slhip_keypoint_vote3d_host(const slhip_keypoint_vote3d_params* pa
                 none(SLHIP_VOTE3D_NO_MODEL);
                 continue;
             }
-            // upwards: lane i % BLOCK meets its supporters in rising order
             const float count = (float)win_support;
-            float lanes[6][BLOCK] = {};
-            for (uint32_t i = 0u; i < n_valid; ++i) {
-                if (!vt::supports(mode, list[i].x, list[i].y, list[i].z, h2)) continue;
-                float acc[3] = {lanes[0][i % BLOCK], lanes[1][i % BLOCK], lanes[2][i % BLOCK]};
-                vt::accumulate_mean(list[i].x, list[i].y, list[i].z, acc);
-                for (int s = 0; s < 3; ++s) lanes[s][i % BLOCK] = acc[s];
-            }
-            const vt::P mean = {slhip_pose::block_sum(lanes[0]) / count, slhip_pose::block_sum(lanes[1]) / count,
-                                slhip_pose::block_sum(lanes[2]) / count};
-            for (int s = 0; s < 3; ++s) std::fill(lanes[s], lanes[s] + BLOCK, 0.0f);
-            for (uint32_t i = 0u; i < n_valid; ++i) {
-                if (!vt::supports(mode, list[i].x, list[i].y, list[i].z, h2)) continue;
-                float acc[6];
-                for (int s = 0; s < 6; ++s) acc[s] = lanes[s][i % BLOCK];
-                vt::accumulate_cov(list[i].x, list[i].y, list[i].z, mean, acc);
-                for (int s = 0; s < 6; ++s) lanes[s][i % BLOCK] = acc[s];
-            }
+            slhip_pose::LaneSums<3> mean_sums;
+            slhip_pose::LaneSums<6> cov_sums;
+            for (uint32_t i = 0u; i < n_valid; ++i)
+                if (vt::supports(mode, list[i].x, list[i].y, list[i].z, h2))
+                    mean_sums.add(i, [&](float* acc) { vt::accumulate_mean(list[i].x, list[i].y, list[i].z, acc); });
+            const vt::P mean = {mean_sums.total(0) / count, mean_sums.total(1) / count, mean_sums.total(2) / count};
+            for (uint32_t i = 0u; i < n_valid; ++i)
+                if (vt::supports(mode, list[i].x, list[i].y, list[i].z, h2))
+                    cov_sums.add(i, [&](float* acc) { vt::accumulate_cov(list[i].x, list[i].y, list[i].z, mean, acc); });
             if (mask & SLHIP_VOTE3D_OUT_SUPPORT) {
                 for (uint32_t w = 0u; w < nw; ++w) out->support[o * nw + w] = 0u;
                 for (uint32_t j = 0u; j < K; ++j)
@@ -482,7 +426,7 @@ extern "C" int slhip_keypoint_vote3d_host(const slhip_keypoint_vote3d_params* pa
             if (mask & SLHIP_VOTE3D_OUT_FLAGS) out->flags[o] = win_stopped ? 0 : SLHIP_VOTE3D_NOT_CONVERGED;
             if (mask & SLHIP_VOTE3D_OUT_MEAN) { out->mean[o * 3u] = mean.x; out->mean[o * 3u + 1u] = mean.y; out->mean[o * 3u + 2u] = mean.z; }
             if (mask & SLHIP_VOTE3D_OUT_COV)
-                for (int s = 0; s < 6; ++s) out->cov[o * 6u + s] = slhip_pose::block_sum(lanes[s]) / count;
+                for (int s = 0; s < 6; ++s) out->cov[o * 6u + s] = cov_sums.total(s) / count;
         }
     return 0;
 }

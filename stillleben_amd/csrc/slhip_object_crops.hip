@@ -189,7 +189,7 @@ extern "C" int slhip_object_crops_timings(float ms_out[2])
                          "slhip_object_crops_select and slhip_object_crops_gather)");
         return -1;
     }
-    return std::min(g_timer.read(ms_out), 0);
+    return g_timer.read_for("slhip_object_crops_timings", ms_out);
 }
 
 extern "C" int slhip_object_crops_check_params(const slhip_object_crop_params* p, int W, int H)

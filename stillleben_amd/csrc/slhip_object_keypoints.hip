@@ -155,14 +155,7 @@ slhip::StepTimer<3> g_timer;
 
 extern "C" int slhip_object_keypoints_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_object_keypoints_timings(float ms_out[3])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_object_keypoints_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_object_keypoints_timings(float ms_out[3]) { return g_timer.read_for("slhip_object_keypoints_timings", ms_out); }
 
 extern "C" int slhip_object_keypoints_check_params(const slhip_object_keypoint_params* p)
 {

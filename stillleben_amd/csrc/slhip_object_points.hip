@@ -212,7 +212,7 @@ extern "C" int slhip_object_points_timings(float ms_out[2])
                          "slhip_object_points_select and slhip_object_points_gather)");
         return -1;
     }
-    return std::min(g_timer.read(ms_out), 0);
+    return g_timer.read_for("slhip_object_points_timings", ms_out);
 }
 
 extern "C" int slhip_object_points_check_params(const slhip_object_point_params* p, int W, int H)

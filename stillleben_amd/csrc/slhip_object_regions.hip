@@ -354,14 +354,7 @@ int check_label(const char* who, const Params* p, const void* instance, const vo
 
 extern "C" int slhip_object_regions_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_object_regions_timings(float ms_out[3])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_object_regions_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_object_regions_timings(float ms_out[3]) { return g_timer.read_for("slhip_object_regions_timings", ms_out); }
 
 extern "C" int slhip_object_regions_check_params(const slhip_object_region_params* p)
 {

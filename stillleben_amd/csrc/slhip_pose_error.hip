@@ -36,7 +36,9 @@ constexpr uint32_t QUERIES = 4u;                       // queries a lane holds i
 constexpr uint32_t QUERY_TILE = BLOCK * QUERIES;       // queries of a workgroup per walk over the targets
 constexpr uint32_t LDS_ARRAYS = 8u;                    // p.x p.y p.z q.x q.y q.z u v, each n_pad floats
 
-__host__ __device__ inline uint32_t pad_to_block(uint32_t n) { return (n + BLOCK - 1u) / BLOCK * BLOCK; }
+using pr::pad_to_block;
+using pr::wave_max;
+using pr::wave_sum;
 
 // min (or max) over the targets [0, count) of dist2(query, target) for NQ queries in registers: four targets per 16-byte read
 // of each coordinate (every lane reads the same address: a broadcast), then the ragged rest one by one
@@ -95,21 +97,6 @@ __device__ __forceinline__ void query_tile_n(uint32_t nq, const float* x, const 
     case 3u: query_tile<3, IS_MAX>(x, y, z, t_x, t_y, t_z, first, count, best); break;
     default: query_tile<4, IS_MAX>(x, y, z, t_x, t_y, t_z, first, count, best); break;
     }
-}
-
-// the butterfly of slhip_pose_rules.h: every lane ends with the wave's sum
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
 }
 
 // the points of class `cls` into LDS, zeros up to the next multiple of BLOCK
@@ -289,8 +276,8 @@ __global__ __launch_bounds__(BLOCK) void k_pose_error(Params p, Bank bank, const
         __syncthreads();
         if (tid == 0u) {
             const float n = (float)count;
-            if (mask & SLHIP_POSE_OUT_ADD) out.add[at] = (((s_sum[0][0] + s_sum[0][1]) + s_sum[0][2]) + s_sum[0][3]) / n;
-            if (mask & SLHIP_POSE_OUT_ADDS) out.adds[at] = (((s_sum[1][0] + s_sum[1][1]) + s_sum[1][2]) + s_sum[1][3]) / n;
+            if (mask & SLHIP_POSE_OUT_ADD) out.add[at] = pr::waves_sum(s_sum[0]) / n;
+            if (mask & SLHIP_POSE_OUT_ADDS) out.adds[at] = pr::waves_sum(s_sum[1]) / n;
             pr::Best b3 = pr::best_start(), b2 = pr::best_start();
             for (uint32_t w = 0u; w < NWAVES; ++w) {
                 pr::Best c;
@@ -377,12 +364,9 @@ int check_call(const char* who, const Params* params, const Bank* bank, const in
         slhip::set_error("%s: class_stride must be at least 1 (1: a plain tensor, 4: slhip_synth_object records)", who);
         return -1;
     }
-    const uint32_t m = params->outputs;
-    if (((m & SLHIP_POSE_OUT_ADD) && !out->add) || ((m & SLHIP_POSE_OUT_ADDS) && !out->adds) ||
-        ((m & SLHIP_POSE_OUT_MSSD) && (!out->mssd || !out->mssd_sym)) || ((m & SLHIP_POSE_OUT_MSPD) && (!out->mspd || !out->mspd_sym))) {
-        slhip::set_error("%s: an output named in `outputs` (0x%x) has a null pointer", who, m);
-        return -1;
-    }
+    const slhip::OutputList outputs = {{SLHIP_POSE_OUT_ADD, out->add},   {SLHIP_POSE_OUT_ADDS, out->adds},     {SLHIP_POSE_OUT_MSSD, out->mssd},
+                                       {SLHIP_POSE_OUT_MSSD, out->mssd_sym}, {SLHIP_POSE_OUT_MSPD, out->mspd}, {SLHIP_POSE_OUT_MSPD, out->mspd_sym}};
+    if (const int st = slhip::check_outputs_present(who, params->outputs, outputs)) return st;
     if (((uintptr_t)classes & 3u) || ((uintptr_t)gt & 3u) || ((uintptr_t)est & 3u)) {
         slhip::set_error("%s: classes, ground truth and estimates must be 4-byte aligned", who);
         return -1;
@@ -401,14 +385,7 @@ slhip::StepTimer<2> g_timer;
 
 extern "C" int slhip_pose_error_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_pose_error_timings(float ms_out[2])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_pose_error_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_pose_error_timings(float ms_out[2]) { return g_timer.read_for("slhip_pose_error_timings", ms_out); }
 
 extern "C" int slhip_pose_error_check_params(const slhip_pose_error_params* p)
 {
@@ -530,17 +507,16 @@ extern "C" int slhip_pose_error_host(const slhip_pose_error_params* params, cons
             }
             q.assign((size_t)count * 3u, 0.0f);
             uv.assign((size_t)count * 2u, 0.0f);
-            float lanes_add[BLOCK] = {}, lanes_adds[BLOCK] = {};
+            pr::LaneSums<1> sum_add, sum_adds;
             bool behind = false;
-            for (int32_t i = 0; i < count; ++i) {      // upwards: lane i % BLOCK meets its points in rising order
+            for (int32_t i = 0; i < count; ++i) {
                 const float x = pts[4 * i], y = pts[4 * i + 1], z = pts[4 * i + 2];
                 float* qi = &q[3 * (size_t)i];
                 const pr::Moved m = pr::move_point(g, D, x, y, z);
                 qi[0] = m.qx;
                 qi[1] = m.qy;
                 qi[2] = m.qz;
-                float& a = lanes_add[(uint32_t)i % BLOCK];
-                a = a + sqrtf(m.add2);
+                sum_add.add((uint32_t)i, [&](float* acc) { acc[0] = acc[0] + sqrtf(m.add2); });
                 if (mask & SLHIP_POSE_OUT_MSPD) {
                     const float X = pr::row_point(e, x, y, z), Y = pr::row_point(e + 4, x, y, z), Z = pr::row_point(e + 8, x, y, z);
                     behind = behind || !(Z > 0.0f);
@@ -551,12 +527,11 @@ extern "C" int slhip_pose_error_host(const slhip_pose_error_params* params, cons
                     float best = inf;
                     for (int32_t j = 0; j < count; ++j)
                         best = fminf(best, pr::dist2(qi[0], qi[1], qi[2], pts[4 * j], pts[4 * j + 1], pts[4 * j + 2]));
-                    float& s = lanes_adds[(uint32_t)i % BLOCK];
-                    s = s + sqrtf(best);
+                    sum_adds.add((uint32_t)i, [&](float* acc) { acc[0] = acc[0] + sqrtf(best); });
                 }
             }
-            if (mask & SLHIP_POSE_OUT_ADD) out->add[at] = pr::block_sum(lanes_add) / (float)count;
-            if (mask & SLHIP_POSE_OUT_ADDS) out->adds[at] = pr::block_sum(lanes_adds) / (float)count;
+            if (mask & SLHIP_POSE_OUT_ADD) out->add[at] = sum_add.total(0) / (float)count;
+            if (mask & SLHIP_POSE_OUT_ADDS) out->adds[at] = sum_adds.total(0) / (float)count;
             if (!(mask & (SLHIP_POSE_OUT_MSSD | SLHIP_POSE_OUT_MSPD))) continue;
             pr::Best b3 = pr::best_start(), b2 = pr::best_start();
             for (int32_t s = 0; s < n_sym; ++s) {

@@ -3,20 +3,19 @@
 // pose from predicted object coordinates plus depth (points.coord onto points.camera).  include/slhip.h "Rigid fit" and
 // DESIGN.md "Rigid fit" are the contract; all arithmetic is float32, one rounded operation at a time (-ffp-contract=off), through
 // slhip_fit_rules.h on host and device alike, so slhip_pose_fit_host gives the kernel's outputs bit for bit.
-//   k_pose_fit   one workgroup of 256 lanes per set.  Three passes over the set's correspondences from global memory (16 bytes a
-//                side; a set is at most 128 KiB and stays in L2), lane l taking j = l, l + 256, ...: the count and the six sums of
-//                the centroids, the nine sums of the moments, the sum of the squared residuals; every sum in pose_error's order.
-//                Between them every lane runs the same 4 x 4 Jacobi in registers, so nothing is broadcast.
+//   k_pose_fit   one workgroup of 256 lanes per set.  The three passes of slhip_fit_block.h over the set's correspondences from
+//                global memory (16 bytes a side; a set is at most 128 KiB and stays in L2), lane l taking j = l, l + 256, ...: the
+//                count and the six sums of the centroids, the nine sums of the moments, the sum of the squared residuals; every
+//                sum in the order of slhip_block_sum.h.  Between them every lane runs the same 4 x 4 Jacobi in registers, so
+//                nothing is broadcast.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdint>
-#include <vector>
 
 #include "slhip.h"
 #include "slhip_checks.h"
 #include "slhip_common.h"
-#include "slhip_fit_rules.h"
+#include "slhip_fit_block.h"
 #include "slhip_step_timer.h"
 
 namespace {
@@ -29,29 +28,6 @@ namespace ft = slhip_fit;
 
 constexpr uint32_t BLOCK = ft::BLOCK;
 constexpr uint32_t NWAVES = BLOCK / ft::WAVE;
-constexpr uint32_t SUMS = 9u;        // the most sums of one reduction (the moments')
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-
-// S[i] = the workgroup's sum of acc[i] in pose_error's order: the butterfly in a wave, then ((w0 + w1) + w2) + w3
-template <int N>
-__device__ __forceinline__ void block_sums(const float* acc, float* s_part, uint32_t wave, uint32_t lane, float* S)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float w = wave_sum(acc[i]);
-        if (lane == 0u) s_part[wave * SUMS + i] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) S[i] = ((s_part[i] + s_part[SUMS + i]) + s_part[2u * SUMS + i]) + s_part[3u * SUMS + i];
-    __syncthreads();      // the sums are read before the next reduction writes them
-}
 
 // lane 0 writes the set's outputs; pose == nullptr: NaN.  (Inlined and unrolled: the pose stays in registers.)
 __device__ __forceinline__ void write_all(const Params& p, const Out& out, uint32_t set, const float* pose, uint32_t n_used, float rms, int flags)
@@ -68,73 +44,32 @@ __device__ __forceinline__ void write_all(const Params& p, const Out& out, uint3
 
 __global__ __launch_bounds__(BLOCK) void k_pose_fit(Params p, const float4* __restrict__ src, const float4* __restrict__ dst, Out out)
 {
-    __shared__ float s_part[NWAVES * SUMS];
+    __shared__ float s_part[NWAVES * ft::FIT_SUMS];
     __shared__ uint32_t s_cnt[NWAVES];
-    const uint32_t N = p.n_points, tid = threadIdx.x, wave = tid / ft::WAVE, lane = tid % ft::WAVE, set = blockIdx.x;
+    const uint32_t N = p.n_points, tid = threadIdx.x, set = blockIdx.x;
     const float4* my_src = src + (size_t)set * N;
     const float4* my_dst = dst + (size_t)set * N;
     const float nan = __builtin_nanf("");
 
-    // pass 1: the count and the centroids
-    float c[6];
-    uint32_t n_used;
-    {
-        float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, S[6];
-        uint32_t mine = 0u;
-        for (uint32_t j = tid; j < N; j += BLOCK) {
-            const float4 a = my_src[j], b = my_dst[j];
-            const float s[4] = {a.x, a.y, a.z, a.w}, d[4] = {b.x, b.y, b.z, b.w};
-            if (!ft::used(s, d)) continue;
-            ++mine;
-            ft::accumulate_centroids(s, d, acc);
-        }
-#pragma unroll
-        for (int off = 32; off; off >>= 1) mine += (uint32_t)__shfl_xor((int)mine, off);
-        if (lane == 0u) s_cnt[wave] = mine;
-        block_sums<6>(acc, s_part, wave, lane, S);      // (its barriers order s_cnt too)
-        n_used = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
-        if (n_used < 3u) {      // the same for every lane
-            write_all(p, out, set, nullptr, n_used, nan, SLHIP_FIT_INSUFFICIENT);
-            return;
-        }
-        const float count = (float)n_used;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) c[i] = S[i] / count;
+    // correspondence j of the set, from global memory
+    auto pair = [&](uint32_t j, float* s, float* d) {
+        const float4 a = my_src[j], b = my_dst[j];
+        s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
+        d[0] = b.x; d[1] = b.y; d[2] = b.z; d[3] = b.w;
+        return ft::used(s, d);
+    };
+    float S[6], pose[12];
+    const uint32_t mine = ft::fit_centroids(N, pair, s_part, S);
+    const uint32_t n_used = slhip_pose::block_count(mine, s_cnt, tid / ft::WAVE, tid % ft::WAVE);
+    if (n_used < 3u) {      // the same for every lane
+        write_all(p, out, set, nullptr, n_used, nan, SLHIP_FIT_INSUFFICIENT);
+        return;
     }
-
-    // pass 2: the moments
-    float M[9];
-    {
-        float acc[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        for (uint32_t j = tid; j < N; j += BLOCK) {
-            const float4 a = my_src[j], b = my_dst[j];
-            const float s[4] = {a.x, a.y, a.z, a.w}, d[4] = {b.x, b.y, b.z, b.w};
-            if (ft::used(s, d)) ft::accumulate_moments(s, d, c, acc);
-        }
-        block_sums<9>(acc, s_part, wave, lane, M);
-    }
-
-    // every lane: the same eigen decomposition, the same pose
-    float A[4][4], V[4][4], pose[12];
-    ft::horn(M, A);
-    ft::jacobi(A, V);
-    if (!ft::pose_of(A, V, c, p.min_gap, pose)) {      // the same for every lane
+    if (!ft::fit_pose(N, pair, S, n_used, p.min_gap, s_part, pose)) {      // the same for every lane
         write_all(p, out, set, nullptr, n_used, nan, SLHIP_FIT_DEGENERATE);
         return;
     }
-
-    // pass 3: the residuals
-    float rms = 0.0f;
-    if (p.outputs & SLHIP_FIT_OUT_RMS) {
-        float acc[1] = {0.0f}, S[1];
-        for (uint32_t j = tid; j < N; j += BLOCK) {
-            const float4 a = my_src[j], b = my_dst[j];
-            const float s[4] = {a.x, a.y, a.z, a.w}, d[4] = {b.x, b.y, b.z, b.w};
-            if (ft::used(s, d)) acc[0] = acc[0] + ft::residual2(pose, s, d);
-        }
-        block_sums<1>(acc, s_part, wave, lane, S);
-        rms = sqrtf(S[0] / (float)n_used);
-    }
+    const float rms = (p.outputs & SLHIP_FIT_OUT_RMS) ? ft::fit_rms(N, pair, pose, n_used, s_part) : 0.0f;
     write_all(p, out, set, pose, n_used, rms, 0);
 }
 
@@ -149,22 +84,14 @@ int check_call(const char* who, const Params* params, const float* src, const fl
         return -1;
     }
     const uint32_t m = params->outputs;
-    if (((m & SLHIP_FIT_OUT_POSE) && !out->pose) || ((m & SLHIP_FIT_OUT_N_USED) && !out->n_used) ||
-        ((m & SLHIP_FIT_OUT_RMS) && !out->rms) || ((m & SLHIP_FIT_OUT_FLAGS) && !out->flags)) {
-        slhip::set_error("%s: an output named in `outputs` (0x%x) has a null pointer", who, m);
-        return -1;
-    }
+    const slhip::OutputList outputs = {
+        {SLHIP_FIT_OUT_POSE, out->pose}, {SLHIP_FIT_OUT_N_USED, out->n_used}, {SLHIP_FIT_OUT_RMS, out->rms}, {SLHIP_FIT_OUT_FLAGS, out->flags}};
+    if (const int st = slhip::check_outputs_present(who, m, outputs)) return st;
     if (((uintptr_t)src & 15u) || ((uintptr_t)dst & 15u)) {
         slhip::set_error("%s: src and dst must be 16-byte aligned", who);
         return -1;
     }
-    const uintptr_t all = ((m & SLHIP_FIT_OUT_POSE) ? (uintptr_t)out->pose : 0u) | ((m & SLHIP_FIT_OUT_N_USED) ? (uintptr_t)out->n_used : 0u) |
-                          ((m & SLHIP_FIT_OUT_RMS) ? (uintptr_t)out->rms : 0u) | ((m & SLHIP_FIT_OUT_FLAGS) ? (uintptr_t)out->flags : 0u);
-    if (all & 3u) {
-        slhip::set_error("%s: every output must be 4-byte aligned", who);
-        return -1;
-    }
-    return 0;
+    return slhip::check_outputs_aligned(who, m, outputs);
 }
 
 // optional HIP-event timing: events round the last call
@@ -174,14 +101,7 @@ slhip::StepTimer<1> g_timer;
 
 extern "C" int slhip_pose_fit_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_pose_fit_timings(float ms_out[1])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_pose_fit_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_pose_fit_timings(float ms_out[1]) { return g_timer.read_for("slhip_pose_fit_timings", ms_out); }
 
 extern "C" int slhip_pose_fit_check_params(const slhip_pose_fit_params* p)
 {
@@ -192,10 +112,7 @@ extern "C" int slhip_pose_fit_check_params(const slhip_pose_fit_params* p)
     }
     if (const int st = slhip::check_range(who, "n_sets", p->n_sets, 0u, 0x7fffffffu)) return st;
     if (const int st = slhip::check_range(who, "n_points", p->n_points, 1u, SLHIP_FIT_POINTS_MAX)) return st;
-    if (!(p->min_gap >= 0.0f) || !(p->min_gap < 1.0f)) {
-        slhip::set_error("%s: min_gap %g must lie in [0, 1)", who, (double)p->min_gap);
-        return -1;
-    }
+    if (const int st = slhip::check_min_gap(who, p->min_gap)) return st;
     if (p->outputs == 0u || (p->outputs & ~ALL_OUTPUTS)) {
         slhip::set_error("%s: outputs 0x%x must name at least one of pose 1, n_used 2, rms 4, flags 8 and nothing else", who, p->outputs);
         return -1;
@@ -233,43 +150,21 @@ extern "C" int slhip_pose_fit_host(const slhip_pose_fit_params* params, const fl
             if (mask & SLHIP_FIT_OUT_RMS) out->rms[set] = rms;
             if (mask & SLHIP_FIT_OUT_FLAGS) out->flags[set] = flags;
         };
-        // upwards: lane j % BLOCK meets its correspondences in rising order
-        float lanes[9][BLOCK] = {};
-        uint32_t n_used = 0u;
-        for (uint32_t j = 0u; j < N; ++j) {
-            if (!ft::used(src + 4u * j, dst + 4u * j)) continue;
-            ++n_used;
-            float acc[6];
-            for (int s = 0; s < 6; ++s) acc[s] = lanes[s][j % BLOCK];
-            ft::accumulate_centroids(src + 4u * j, dst + 4u * j, acc);
-            for (int s = 0; s < 6; ++s) lanes[s][j % BLOCK] = acc[s];
-        }
-        if (n_used < 3u) {
+        auto pair = [&](uint32_t j, float* s, float* d) {
+            for (int i = 0; i < 4; ++i) {
+                s[i] = src[4u * j + i];
+                d[i] = dst[4u * j + i];
+            }
+            return ft::used(s, d);
+        };
+        float S[6], pose[12];
+        const uint32_t n_used = ft::fit_centroids_host(N, pair, S);
+        if (n_used < 3u)
             write(nullptr, n_used, nan, SLHIP_FIT_INSUFFICIENT);
-            continue;
-        }
-        float c[6], M[9];
-        for (int s = 0; s < 6; ++s) c[s] = slhip_pose::block_sum(lanes[s]) / (float)n_used;
-        for (int s = 0; s < 9; ++s) std::fill(lanes[s], lanes[s] + BLOCK, 0.0f);
-        for (uint32_t j = 0u; j < N; ++j) {
-            if (!ft::used(src + 4u * j, dst + 4u * j)) continue;
-            float acc[9];
-            for (int s = 0; s < 9; ++s) acc[s] = lanes[s][j % BLOCK];
-            ft::accumulate_moments(src + 4u * j, dst + 4u * j, c, acc);
-            for (int s = 0; s < 9; ++s) lanes[s][j % BLOCK] = acc[s];
-        }
-        for (int s = 0; s < 9; ++s) M[s] = slhip_pose::block_sum(lanes[s]);
-        float A[4][4], V[4][4], pose[12];
-        ft::horn(M, A);
-        ft::jacobi(A, V);
-        if (!ft::pose_of(A, V, c, p.min_gap, pose)) {
+        else if (!ft::fit_pose_host(N, pair, S, n_used, p.min_gap, pose))
             write(nullptr, n_used, nan, SLHIP_FIT_DEGENERATE);
-            continue;
-        }
-        std::fill(lanes[0], lanes[0] + BLOCK, 0.0f);
-        for (uint32_t j = 0u; j < N; ++j)
-            if (ft::used(src + 4u * j, dst + 4u * j)) lanes[0][j % BLOCK] = lanes[0][j % BLOCK] + ft::residual2(pose, src + 4u * j, dst + 4u * j);
-        write(pose, n_used, sqrtf(slhip_pose::block_sum(lanes[0]) / (float)n_used), 0);
+        else
+            write(pose, n_used, ft::fit_rms_host(N, pair, pose, n_used), 0);
     }
     return 0;
 }

@@ -7,7 +7,7 @@
 //                never transformed.  Per iteration  (A) association: a lane holds up to four camera points in registers, in the
 //                object frame of the current pose, and walks the bank by broadcast 16-byte LDS reads (the walk of
 //                slhip_pose_error.hip (B), restated with the index of the minimum); the matched index of every point goes to LDS,
-//                (B) the fit of slhip_pose_fit.hip over the pairs: the count and the centroids, the moments, then every lane the
+//                (B) the fit of slhip_fit_block.h over the pairs: the count and the centroids, the moments, then every lane the
 //                same 4 x 4 Jacobi in registers,  (C) lane 0 writes the stop word, every lane reads it behind a barrier.  The
 //                residuals are summed once, for the pose the loop ends with.  No float atomics; the loop runs max_iters times at
 //                the most.
@@ -20,6 +20,7 @@
 #include "slhip.h"
 #include "slhip_checks.h"
 #include "slhip_common.h"
+#include "slhip_fit_block.h"
 #include "slhip_icp_rules.h"
 #include "slhip_step_timer.h"
 
@@ -32,39 +33,15 @@ using Bank = slhip_pose_bank;
 using Out = slhip_pose_icp_out;
 namespace ic = slhip_icp;
 namespace ft = slhip_fit;
+using slhip_pose::pad_to_block;
 
 constexpr uint32_t BLOCK = ic::BLOCK;
 constexpr uint32_t NWAVES = BLOCK / ic::WAVE;
-constexpr uint32_t SUMS = 9u;                          // the most sums of one reduction (the moments')
 constexpr uint32_t QUERIES = 4u;                       // camera points a lane holds in registers in the walk
 constexpr uint32_t QUERY_TILE = BLOCK * QUERIES;       // camera points of a workgroup per walk over the bank
 
-__host__ __device__ inline uint32_t pad_to_block(uint32_t n) { return (n + BLOCK - 1u) / BLOCK * BLOCK; }
-
 // dynamic LDS of a launch: the bank's three coordinate arrays and the K matched indices (at most 48 KiB + 16 KiB)
 inline size_t lds_bytes(uint32_t bank_points, uint32_t K) { return ((size_t)3u * pad_to_block(bank_points) + K) * 4u; }
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-
-// S[i] = the workgroup's sum of acc[i] in pose_error's order: the butterfly in a wave, then ((w0 + w1) + w2) + w3
-template <int N>
-__device__ __forceinline__ void block_sums(const float* acc, float* s_part, uint32_t wave, uint32_t lane, float* S)
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float w = wave_sum(acc[i]);
-        if (lane == 0u) s_part[wave * SUMS + i] = w;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) S[i] = ((s_part[i] + s_part[SUMS + i]) + s_part[2u * SUMS + i]) + s_part[3u * SUMS + i];
-    __syncthreads();      // the sums are read before the next reduction writes them
-}
 
 // rule 4 for NQ queries in registers: four bank points per 16-byte read of each coordinate (every lane reads the same address:
 // a broadcast), then the ragged rest one by one; upwards, so the lowest index of the smallest distance stays
@@ -134,24 +111,12 @@ __device__ __forceinline__ uint32_t associate_n(uint32_t nq, const float* pose, 
     }
 }
 
-// the pair of camera point j: false when it has none
-__device__ __forceinline__ bool pair_of(const int32_t* s_near, const float* s_x, const float* s_y, const float* s_z,
-                                        const float4* __restrict__ cam, uint32_t j, float* s, float* d)
-{
-    const int32_t m = s_near[j];
-    if (m < 0) return false;
-    const float4 c = cam[j];
-    s[0] = s_x[m]; s[1] = s_y[m]; s[2] = s_z[m]; s[3] = 1.0f;
-    d[0] = c.x; d[1] = c.y; d[2] = c.z; d[3] = c.w;
-    return true;
-}
-
 // Dynamic LDS: 3 * n_pad floats (the bank's x, y, z) and K int32 (the matched indices).
 __global__ __launch_bounds__(BLOCK) void k_pose_icp(Params p, const float4* __restrict__ camera, const float* __restrict__ init,
                                                     const int32_t* __restrict__ classes, Bank bank, Out out, uint32_t n_pad)
 {
     extern __shared__ __attribute__((aligned(16))) float s_all[];
-    __shared__ float s_part[NWAVES * SUMS];
+    __shared__ float s_part[NWAVES * ft::FIT_SUMS];
     __shared__ uint32_t s_cnt[NWAVES];
     __shared__ int s_word[2];      // [0] the stop and failure decision of lane 0, [1] the class's count
     float* s_x = s_all;
@@ -162,6 +127,16 @@ __global__ __launch_bounds__(BLOCK) void k_pose_icp(Params p, const float4* __re
     const uint32_t K = p.n_points, tid = threadIdx.x, wave = tid / ic::WAVE, lane = tid % ic::WAVE, set = blockIdx.x, mask = p.outputs;
     const float4* cam = camera + (size_t)set * K;
     const float nan = __builtin_nanf("");
+
+    // the pair of camera point j: false when it has none
+    auto pair = [&](uint32_t j, float* s, float* d) {
+        const int32_t m = s_near[j];
+        if (m < 0) return false;
+        const float4 c = cam[j];
+        s[0] = s_x[m]; s[1] = s_y[m]; s[2] = s_z[m]; s[3] = 1.0f;
+        d[0] = c.x; d[1] = c.y; d[2] = c.z; d[3] = c.w;
+        return true;
+    };
 
     float pose[12];
 #pragma unroll
@@ -202,44 +177,17 @@ __global__ __launch_bounds__(BLOCK) void k_pose_icp(Params p, const float4* __re
                 const uint32_t nq = min(QUERIES, (K - first + BLOCK - 1u) / BLOCK);
                 mine += associate_n(nq, pose, cam, first, K, gate, s_x, s_y, s_z, count, s_near);
             }
-#pragma unroll
-            for (int off = 32; off; off >>= 1) mine += (uint32_t)__shfl_xor((int)mine, off);
-            if (lane == 0u) s_cnt[wave] = mine;
 
-            // (B) the fit over the pairs: the count and the centroids
-            float c[6];
-            {
-                float acc[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, S[6];
-                __syncthreads();      // the matched indices are in LDS
-                for (uint32_t j = tid; j < K; j += BLOCK) {
-                    float s[4], d[4];
-                    if (pair_of(s_near, s_x, s_y, s_z, cam, j, s, d)) ft::accumulate_centroids(s, d, acc);
-                }
-                block_sums<6>(acc, s_part, wave, lane, S);      // (its barriers order s_cnt too)
-                n_pairs = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3]));
-                if (n_pairs < p.min_pairs) {      // the same for every lane
-                    flags = SLHIP_ICP_INSUFFICIENT;
-                    have_pose = false;
-                    break;
-                }
-                const float n = (float)n_pairs;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) c[i] = S[i] / n;
+            // (B) the fit over the pairs (the barrier of the count also puts the matched indices in LDS)
+            n_pairs = (uint32_t)__builtin_amdgcn_readfirstlane((int)slhip_pose::block_count(mine, s_cnt, wave, lane));
+            if (n_pairs < p.min_pairs) {      // the same for every lane
+                flags = SLHIP_ICP_INSUFFICIENT;
+                have_pose = false;
+                break;
             }
-            float M[9];
-            {
-                float acc[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-                for (uint32_t j = tid; j < K; j += BLOCK) {
-                    float s[4], d[4];
-                    if (pair_of(s_near, s_x, s_y, s_z, cam, j, s, d)) ft::accumulate_moments(s, d, c, acc);
-                }
-                block_sums<9>(acc, s_part, wave, lane, M);
-            }
-            // every lane: the same eigen decomposition, the same pose
-            float A[4][4], V[4][4], next[12];
-            ft::horn(M, A);
-            ft::jacobi(A, V);
-            const bool fitted = ft::pose_of(A, V, c, p.min_gap, next);
+            float S[6], next[12];
+            ft::fit_centroids(K, pair, s_part, S);
+            const bool fitted = ft::fit_pose(K, pair, S, n_pairs, p.min_gap, s_part, next);
 
             // (C) lane 0 decides, every lane reads the decision behind a barrier
             if (tid == 0u) s_word[0] = !fitted ? SLHIP_ICP_DEGENERATE : ic::converged(pose, next, p.tol_rot, p.tol_trans) ? SLHIP_ICP_CONVERGED : 0;
@@ -257,15 +205,7 @@ __global__ __launch_bounds__(BLOCK) void k_pose_icp(Params p, const float4* __re
             gate = ic::next_gate(gate, p.dist_scale, p.min_dist);
             if ((stop & SLHIP_ICP_CONVERGED) || iters == p.max_iters) {
                 flags = stop & SLHIP_ICP_CONVERGED;
-                if (mask & SLHIP_ICP_OUT_RMS) {      // rule 7, once: for the pose the loop ends with
-                    float acc[1] = {0.0f}, S[1];
-                    for (uint32_t j = tid; j < K; j += BLOCK) {
-                        float s[4], d[4];
-                        if (pair_of(s_near, s_x, s_y, s_z, cam, j, s, d)) acc[0] = acc[0] + ft::residual2(pose, s, d);
-                    }
-                    block_sums<1>(acc, s_part, wave, lane, S);
-                    rms = sqrtf(S[0] / (float)n_pairs);
-                }
+                if (mask & SLHIP_ICP_OUT_RMS) rms = ft::fit_rms(K, pair, pose, n_pairs, s_part);      // rule 7, once: for the pose the loop ends with
                 break;
             }
         }
@@ -306,12 +246,9 @@ int check_call(const char* who, const Params* params, const float* camera, const
         return -1;
     }
     const uint32_t m = params->outputs;
-    if (((m & SLHIP_ICP_OUT_POSE) && !out->pose) || ((m & SLHIP_ICP_OUT_N_PAIRS) && !out->n_pairs) || ((m & SLHIP_ICP_OUT_RMS) && !out->rms) ||
-        ((m & SLHIP_ICP_OUT_ITERS) && !out->iters) || ((m & SLHIP_ICP_OUT_FLAGS) && !out->flags) ||
-        ((m & SLHIP_ICP_OUT_NEAREST) && !out->nearest)) {
-        slhip::set_error("%s: an output named in `outputs` (0x%x) has a null pointer", who, m);
-        return -1;
-    }
+    const slhip::OutputList outputs = {{SLHIP_ICP_OUT_POSE, out->pose},   {SLHIP_ICP_OUT_N_PAIRS, out->n_pairs}, {SLHIP_ICP_OUT_RMS, out->rms},
+                                       {SLHIP_ICP_OUT_ITERS, out->iters}, {SLHIP_ICP_OUT_FLAGS, out->flags},     {SLHIP_ICP_OUT_NEAREST, out->nearest}};
+    if (const int st = slhip::check_outputs_present(who, m, outputs)) return st;
     if (((uintptr_t)camera & 15u) || ((uintptr_t)init & 15u) || ((uintptr_t)b->points & 15u)) {
         slhip::set_error("%s: camera, init and the bank's points must be 16-byte aligned", who);
         return -1;
@@ -320,13 +257,7 @@ int check_call(const char* who, const Params* params, const float* camera, const
         slhip::set_error("%s: classes and the bank's count must be 4-byte aligned", who);
         return -1;
     }
-    const uintptr_t all = ((m & SLHIP_ICP_OUT_POSE) ? (uintptr_t)out->pose : 0u) | ((m & SLHIP_ICP_OUT_N_PAIRS) ? (uintptr_t)out->n_pairs : 0u) |
-                          ((m & SLHIP_ICP_OUT_RMS) ? (uintptr_t)out->rms : 0u) | ((m & SLHIP_ICP_OUT_ITERS) ? (uintptr_t)out->iters : 0u) |
-                          ((m & SLHIP_ICP_OUT_FLAGS) ? (uintptr_t)out->flags : 0u) | ((m & SLHIP_ICP_OUT_NEAREST) ? (uintptr_t)out->nearest : 0u);
-    if (all & 3u) {
-        slhip::set_error("%s: every output must be 4-byte aligned", who);
-        return -1;
-    }
+    if (const int st = slhip::check_outputs_aligned(who, m, outputs)) return st;
     if (const int st = slhip::check_range(who, "the bank's n_assets", b->n_assets, 1u, SLHIP_SYNTH_MAX_ASSETS)) return st;
     return slhip::check_range(who, "the bank's n_points", b->n_points, 1u, SLHIP_POSE_POINTS_MAX);
 }
@@ -338,14 +269,7 @@ slhip::StepTimer<1> g_timer;
 
 extern "C" int slhip_pose_icp_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_pose_icp_timings(float ms_out[1])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_pose_icp_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_pose_icp_timings(float ms_out[1]) { return g_timer.read_for("slhip_pose_icp_timings", ms_out); }
 
 extern "C" int slhip_pose_icp_check_params(const slhip_pose_icp_params* p)
 {
@@ -370,10 +294,7 @@ extern "C" int slhip_pose_icp_check_params(const slhip_pose_icp_params* p)
         slhip::set_error("%s: min_dist %g must be at least 0", who, (double)p->min_dist);
         return -1;
     }
-    if (!(p->min_gap >= 0.0f) || !(p->min_gap < 1.0f)) {
-        slhip::set_error("%s: min_gap %g must lie in [0, 1)", who, (double)p->min_gap);
-        return -1;
-    }
+    if (const int st = slhip::check_min_gap(who, p->min_gap)) return st;
     if (!at_least_zero(p->tol_rot)) {
         slhip::set_error("%s: tol_rot %g must be at least 0", who, (double)p->tol_rot);
         return -1;
@@ -431,7 +352,7 @@ extern "C" int slhip_pose_icp_host(const slhip_pose_icp_params* params, const fl
             const float* pts = b->points + (size_t)cls * b->n_points * 4u;
             float gate = p.max_dist;
             // the pair of camera point j: false when it has none
-            auto pair_of = [&](uint32_t j, float* s, float* d) {
+            auto pair = [&](uint32_t j, float* s, float* d) {
                 const int32_t m = near[j];
                 if (m < 0) return false;
                 s[0] = pts[4 * m]; s[1] = pts[4 * m + 1]; s[2] = pts[4 * m + 2]; s[3] = 1.0f;
@@ -455,31 +376,9 @@ extern "C" int slhip_pose_icp_host(const slhip_pose_icp_params* params, const fl
                     have_pose = false;
                     break;
                 }
-                // upwards: lane j % BLOCK meets its pairs in rising order
-                float lanes[9][BLOCK] = {};
-                float s[4], d[4];
-                for (uint32_t j = 0u; j < K; ++j) {
-                    if (!pair_of(j, s, d)) continue;
-                    float acc[6];
-                    for (int i = 0; i < 6; ++i) acc[i] = lanes[i][j % BLOCK];
-                    ft::accumulate_centroids(s, d, acc);
-                    for (int i = 0; i < 6; ++i) lanes[i][j % BLOCK] = acc[i];
-                }
-                float c[6], M[9];
-                for (int i = 0; i < 6; ++i) c[i] = slhip_pose::block_sum(lanes[i]) / (float)n_pairs;
-                for (int i = 0; i < 9; ++i) std::fill(lanes[i], lanes[i] + BLOCK, 0.0f);
-                for (uint32_t j = 0u; j < K; ++j) {
-                    if (!pair_of(j, s, d)) continue;
-                    float acc[9];
-                    for (int i = 0; i < 9; ++i) acc[i] = lanes[i][j % BLOCK];
-                    ft::accumulate_moments(s, d, c, acc);
-                    for (int i = 0; i < 9; ++i) lanes[i][j % BLOCK] = acc[i];
-                }
-                for (int i = 0; i < 9; ++i) M[i] = slhip_pose::block_sum(lanes[i]);
-                float A[4][4], V[4][4], next[12];
-                ft::horn(M, A);
-                ft::jacobi(A, V);
-                if (!ft::pose_of(A, V, c, p.min_gap, next)) {
+                float S[6], next[12];
+                ft::fit_centroids_host(K, pair, S);
+                if (!ft::fit_pose_host(K, pair, S, n_pairs, p.min_gap, next)) {
                     flags = SLHIP_ICP_DEGENERATE;
                     have_pose = false;
                     break;
@@ -491,10 +390,7 @@ extern "C" int slhip_pose_icp_host(const slhip_pose_icp_params* params, const fl
                 gate = ic::next_gate(gate, p.dist_scale, p.min_dist);
                 if (conv || iters == p.max_iters) {
                     flags = conv ? SLHIP_ICP_CONVERGED : 0;
-                    std::fill(lanes[0], lanes[0] + BLOCK, 0.0f);
-                    for (uint32_t j = 0u; j < K; ++j)
-                        if (pair_of(j, s, d)) lanes[0][j % BLOCK] = lanes[0][j % BLOCK] + ft::residual2(pose, s, d);
-                    rms = sqrtf(slhip_pose::block_sum(lanes[0]) / (float)n_pairs);
+                    rms = ft::fit_rms_host(K, pair, pose, n_pairs);
                     break;
                 }
             }

@@ -6,7 +6,7 @@
 //                (u, v, x, y, z) by ballot ranks;  (2) a lane per hypothesis in rounds of 256: Philox, P3P, then the score with
 //                the twelve pose entries in registers and the points by 16-byte LDS reads at one address for all lanes (a
 //                broadcast), no barrier inside a round;  (3) arg-max of (count, lowest index) by wave then workgroup;
-//                (4) Gauss-Newton: lanes over points, 27 sums in pose_error's order, every lane solves the 6 x 6;
+//                (4) Gauss-Newton: lanes over points, 27 sums in the order of slhip_block_sum.h, every lane solves the 6 x 6;
 //                (5) the final pass over the correspondences in their own order: ballot words, count, rms
 #include <hip/hip_runtime.h>
 
@@ -31,23 +31,10 @@ namespace pn = slhip_pnp;
 constexpr uint32_t BLOCK = pn::BLOCK;
 constexpr uint32_t NWAVES = BLOCK / pn::WAVE;
 constexpr uint32_t PLANES = 5u;      // u v x y z, each k_pad floats
+constexpr int PART_STRIDE = pn::SUMS + 1;      // the words of a wave's row of partial sums
 
-__host__ __device__ inline uint32_t pad4(uint32_t n) { return (n + 3u) & ~3u; }
-__host__ __device__ inline uint32_t words_of(uint32_t K) { return (K + 31u) / 32u; }
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
-    return v;
-}
+using slhip_pose::pad4;
+using slhip_pose::words_of;
 
 __device__ __forceinline__ pn::Camera camera_of(const Params& p, const float* intrinsics, uint32_t set)
 {
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(BLOCK) void k_pose_pnp(Params p, const float* __res
     __shared__ uint32_t s_cnt[NWAVES];
     __shared__ uint32_t s_key[NWAVES];
     __shared__ float s_pose[12];
-    __shared__ float s_part[NWAVES][pn::SUMS + 1];
+    __shared__ float s_part[NWAVES * PART_STRIDE];
     float* s_u = s_all;
     float* s_v = s_u + k_pad;
     float* s_x = s_v + k_pad;
@@ -182,7 +169,7 @@ __global__ __launch_bounds__(BLOCK) void k_pose_pnp(Params p, const float* __res
     }
 
     // (3) the winner: highest count, then lowest slot; every real slot has a key of its own, so one lane owns the maximum
-    const uint32_t wkey = wave_max(best_key);
+    const uint32_t wkey = slhip_pose::wave_max(best_key);
     if (lane == 0u) s_key[wave] = wkey;
     __syncthreads();
     const uint32_t win = max(max(s_key[0], s_key[1]), max(s_key[2], s_key[3]));
@@ -203,7 +190,7 @@ __global__ __launch_bounds__(BLOCK) void k_pose_pnp(Params p, const float* __res
 
     // (4) Gauss-Newton on the inliers of the current pose: lane l takes valid points l, l + 256, ...
     for (uint32_t it = 0u; it < p.refine_iters; ++it) {
-        float acc[pn::SUMS];
+        float acc[pn::SUMS], S[pn::SUMS];
 #pragma unroll
         for (int i = 0; i < pn::SUMS; ++i) acc[i] = 0.0f;
         for (uint32_t i = tid; i < n_valid; i += BLOCK) {
@@ -211,16 +198,7 @@ __global__ __launch_bounds__(BLOCK) void k_pose_pnp(Params p, const float* __res
             if (pn::inlier(M, cam, s_x[i], s_y[i], s_z[i], s_u[i], s_v[i], thr2, &e2))
                 pn::accumulate(M, cam, s_x[i], s_y[i], s_z[i], s_u[i], s_v[i], acc);
         }
-#pragma unroll
-        for (int i = 0; i < pn::SUMS; ++i) {
-            const float w = wave_sum(acc[i]);
-            if (lane == 0u) s_part[wave][i] = w;
-        }
-        __syncthreads();
-        float S[pn::SUMS];
-#pragma unroll
-        for (int i = 0; i < pn::SUMS; ++i) S[i] = ((s_part[0][i] + s_part[1][i]) + s_part[2][i]) + s_part[3][i];
-        __syncthreads();      // the sums are read before the next step writes them
+        slhip_pose::block_sums<pn::SUMS, PART_STRIDE>(acc, s_part, wave, lane, S);
         if (!pn::step(S, M)) {      // the same for every lane
             flags |= SLHIP_PNP_REFINE_STOPPED;
             break;
@@ -251,14 +229,15 @@ __global__ __launch_bounds__(BLOCK) void k_pose_pnp(Params p, const float* __res
                 if (w0 + 1u < nw) out.inliers[(size_t)set * nw + w0 + 1u] = (uint32_t)(votes >> 32);
             }
         }
-        const float w = wave_sum(acc);
+        // (the count is read between the barriers of its own: the next pass writes s_cnt with no barrier in front)
+        const float w = slhip_pose::wave_sum(acc);
         if (lane == 0u) {
-            s_part[wave][0] = w;
+            s_part[wave * PART_STRIDE] = w;
             s_cnt[wave] = mine;
         }
         __syncthreads();
-        const uint32_t count = ((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3];
-        const float sum = ((s_part[0][0] + s_part[1][0]) + s_part[2][0]) + s_part[3][0];
+        const uint32_t count = slhip_pose::waves_sum(s_cnt);
+        const float sum = slhip_pose::waves_sum(s_part, PART_STRIDE);
         __syncthreads();
         if (pass == 0 && count < win_count) {      // the same for every lane; only a refined pose can get here
             flags |= SLHIP_PNP_REFINE_REJECTED;
@@ -294,13 +273,9 @@ int check_call(const char* who, const Params* params, const float* uv, const flo
         slhip::set_error("%s: n_hypotheses 0 needs an initial pose (a pure refinement); without one there is nothing to score", who);
         return -1;
     }
-    const uint32_t m = params->outputs;
-    if (((m & SLHIP_PNP_OUT_POSE) && !out->pose) || ((m & SLHIP_PNP_OUT_N_INLIERS) && !out->n_inliers) ||
-        ((m & SLHIP_PNP_OUT_RMS) && !out->rms) || ((m & SLHIP_PNP_OUT_INLIERS) && !out->inliers) ||
-        ((m & SLHIP_PNP_OUT_BEST) && !out->best) || ((m & SLHIP_PNP_OUT_FLAGS) && !out->flags)) {
-        slhip::set_error("%s: an output named in `outputs` (0x%x) has a null pointer", who, m);
-        return -1;
-    }
+    const slhip::OutputList outputs = {{SLHIP_PNP_OUT_POSE, out->pose},       {SLHIP_PNP_OUT_N_INLIERS, out->n_inliers}, {SLHIP_PNP_OUT_RMS, out->rms},
+                                       {SLHIP_PNP_OUT_INLIERS, out->inliers}, {SLHIP_PNP_OUT_BEST, out->best},           {SLHIP_PNP_OUT_FLAGS, out->flags}};
+    if (const int st = slhip::check_outputs_present(who, params->outputs, outputs)) return st;
     if (((uintptr_t)uv & 7u) || ((uintptr_t)xyz & 15u) || ((uintptr_t)intrinsics & 15u) || ((uintptr_t)init & 3u)) {
         slhip::set_error("%s: uv must be 8-byte aligned, xyz and the intrinsics 16-byte, the initial poses 4-byte", who);
         return -1;
@@ -316,14 +291,7 @@ slhip::StepTimer<2> g_timer;
 
 extern "C" int slhip_pose_pnp_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_pose_pnp_timings(float ms_out[2])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_pose_pnp_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_pose_pnp_timings(float ms_out[2]) { return g_timer.read_for("slhip_pose_pnp_timings", ms_out); }
 
 extern "C" int slhip_pose_pnp_check_params(const slhip_pose_pnp_params* p)
 {
@@ -461,24 +429,22 @@ extern "C" int slhip_pose_pnp_host(const slhip_pose_pnp_params* params, const fl
         for (int i = 0; i < 12; ++i) M[i] = W[i];
         int flags = 0;
         for (uint32_t it = 0u; it < p.refine_iters; ++it) {
-            std::vector<float> lanes((size_t)pn::SUMS * BLOCK, 0.0f);      // lanes[s * BLOCK + l]
-            for (uint32_t i = 0u; i < n_valid; ++i) {      // upwards: lane i % BLOCK meets its points in rising order
+            slhip_pose::LaneSums<pn::SUMS> sums;
+            for (uint32_t i = 0u; i < n_valid; ++i) {
                 const float* c = &list[(size_t)i * 5u];
-                float e2, acc[pn::SUMS];
-                if (!pn::inlier(M, cam, c[2], c[3], c[4], c[0], c[1], thr2, &e2)) continue;
-                for (int s = 0; s < pn::SUMS; ++s) acc[s] = lanes[(size_t)s * BLOCK + i % BLOCK];
-                pn::accumulate(M, cam, c[2], c[3], c[4], c[0], c[1], acc);
-                for (int s = 0; s < pn::SUMS; ++s) lanes[(size_t)s * BLOCK + i % BLOCK] = acc[s];
+                float e2;
+                if (pn::inlier(M, cam, c[2], c[3], c[4], c[0], c[1], thr2, &e2))
+                    sums.add(i, [&](float* acc) { pn::accumulate(M, cam, c[2], c[3], c[4], c[0], c[1], acc); });
             }
             float S[pn::SUMS];
-            for (int s = 0; s < pn::SUMS; ++s) S[s] = slhip_pose::block_sum(&lanes[(size_t)s * BLOCK]);
+            for (int s = 0; s < pn::SUMS; ++s) S[s] = sums.total(s);
             if (!pn::step(S, M)) {
                 flags |= SLHIP_PNP_REFINE_STOPPED;
                 break;
             }
         }
         for (int pass = 0; pass < 2; ++pass) {
-            float lanes[BLOCK] = {};
+            slhip_pose::LaneSums<1> sums;
             uint32_t count = 0u;
             std::vector<uint32_t> bits(nw, 0u);
             for (uint32_t j = 0u; j < K; ++j) {
@@ -486,7 +452,7 @@ extern "C" int slhip_pose_pnp_host(const slhip_pose_pnp_params* params, const fl
                 if (!pn::valid(uv[2 * j], uv[2 * j + 1], xyz[4 * j], xyz[4 * j + 1], xyz[4 * j + 2], xyz[4 * j + 3]) ||
                     !pn::inlier(M, cam, xyz[4 * j], xyz[4 * j + 1], xyz[4 * j + 2], uv[2 * j], uv[2 * j + 1], thr2, &e2))
                     continue;
-                lanes[j % BLOCK] = lanes[j % BLOCK] + e2;
+                sums.add(j, [&](float* acc) { acc[0] = acc[0] + e2; });
                 bits[j >> 5] |= 1u << (j & 31u);
                 ++count;
             }
@@ -500,7 +466,7 @@ extern "C" int slhip_pose_pnp_host(const slhip_pose_pnp_params* params, const fl
             if (mask & SLHIP_PNP_OUT_POSE)
                 for (int i = 0; i < 12; ++i) out->pose[(size_t)set * 12u + i] = M[i];
             if (mask & SLHIP_PNP_OUT_N_INLIERS) out->n_inliers[set] = (int32_t)count;
-            if (mask & SLHIP_PNP_OUT_RMS) out->rms[set] = sqrtf(slhip_pose::block_sum(lanes) / (float)count);
+            if (mask & SLHIP_PNP_OUT_RMS) out->rms[set] = sqrtf(sums.total(0) / (float)count);
             if (mask & SLHIP_PNP_OUT_BEST) out->best[set] = pn::key_best(win);
             if (mask & SLHIP_PNP_OUT_FLAGS) out->flags[set] = flags;
             break;

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "slhip.h"
+#include "slhip_block_sum.h"           // BLOCK, WAVE, block_sum: the two means are sums in its order, / (float)count
 #include "slhip_keypoint_rules.h"      // row_point, is_finite
 
 namespace slhip_pose {
@@ -26,8 +27,6 @@ namespace slhip_pose {
 using slhip_kp::is_finite;
 using slhip_kp::row_point;
 
-constexpr uint32_t BLOCK = 256u;      // the lanes of a pose pair's sums: lane l takes points l, l + 256, l + 512, ... upwards
-constexpr uint32_t WAVE = 64u;
 constexpr int NONE = 0x7fffffff;
 
 SLHIP_HD void difference(const float* g, const float* e, float* D)
@@ -99,24 +98,5 @@ SLHIP_HD Best best_start()
 SLHIP_HD Best join(const Best& a, const Best& b) { return (b.val < a.val || (b.val == a.val && b.idx < a.idx)) ? b : a; }
 
 SLHIP_HD int best_index(const Best& b) { return b.idx == NONE ? -1 : b.idx; }
-
-// The two means.  Lane l of BLOCK starts from 0.0f and adds the terms of its points l, l + BLOCK, ... in that order; a lane
-// without points keeps 0.0f.  The lanes of a wave (64 consecutive lanes) combine by the butterfly
-//   for off = 32, 16, 8, 4, 2, 1:  v[l] = v[l] + v[l ^ off]      (all lanes at once: every lane ends with the wave's sum)
-// the four waves as ((w0 + w1) + w2) + w3, and the mean is that sum / (float)count.  Host form of the combination:
-inline float block_sum(const float* lanes)
-{
-    float w[BLOCK / WAVE];
-    for (uint32_t k = 0; k < BLOCK / WAVE; ++k) {
-        float v[WAVE], n[WAVE];
-        for (uint32_t l = 0; l < WAVE; ++l) v[l] = lanes[k * WAVE + l];
-        for (uint32_t off = WAVE / 2u; off; off >>= 1) {
-            for (uint32_t l = 0; l < WAVE; ++l) n[l] = v[l] + v[l ^ off];
-            for (uint32_t l = 0; l < WAVE; ++l) v[l] = n[l];
-        }
-        w[k] = v[0];
-    }
-    return ((w[0] + w[1]) + w[2]) + w[3];
-}
 
 }  // namespace slhip_pose

@@ -411,12 +411,9 @@ int check_vsd_call(const char* who, const Params* params, const Surface* s, cons
         slhip::set_error("%s: estimates and the scene's depth must be 4-byte aligned", who);
         return -1;
     }
-    const uint32_t m = params->outputs;
-    if (((m & SLHIP_VSD_OUT_VSD) && !out->vsd) || ((m & SLHIP_VSD_OUT_COUNTS) && !out->counts) ||
-        ((m & SLHIP_VSD_OUT_COST) && !out->n_cost) || ((m & SLHIP_VSD_OUT_FLAGS) && !out->flags)) {
-        slhip::set_error("%s: an output named in `outputs` (0x%x) has a null pointer", who, m);
-        return -1;
-    }
+    const slhip::OutputList outputs = {
+        {SLHIP_VSD_OUT_VSD, out->vsd}, {SLHIP_VSD_OUT_COUNTS, out->counts}, {SLHIP_VSD_OUT_COST, out->n_cost}, {SLHIP_VSD_OUT_FLAGS, out->flags}};
+    if (const int st = slhip::check_outputs_present(who, params->outputs, outputs)) return st;
     if (((uintptr_t)out->vsd & 3u) || ((uintptr_t)out->counts & 3u) || ((uintptr_t)out->n_cost & 3u) || ((uintptr_t)out->flags & 3u)) {
         slhip::set_error("%s: the outputs must be 4-byte aligned", who);
         return -1;
@@ -471,14 +468,7 @@ extern "C" int slhip_pose_vsd_band_pixels(void) { return (int)BAND_PIXELS; }
 
 extern "C" int slhip_pose_vsd_timing_enable(int on) { return g_timer.enable(on); }
 
-extern "C" int slhip_pose_vsd_timings(float ms_out[2])
-{
-    if (!ms_out) {
-        slhip::set_error("slhip_pose_vsd_timings: null argument");
-        return -1;
-    }
-    return std::min(g_timer.read(ms_out), 0);
-}
+extern "C" int slhip_pose_vsd_timings(float ms_out[2]) { return g_timer.read_for("slhip_pose_vsd_timings", ms_out); }
 
 extern "C" int slhip_pose_vsd_check_params(const slhip_pose_vsd_params* p)
 {

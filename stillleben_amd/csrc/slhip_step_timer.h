@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "slhip_common.h"
 
 namespace slhip {
@@ -54,6 +56,15 @@ struct StepTimer {
             ++n;
         }
         return n;
+    }
+    // the body of an entry slhip_<module>_timings(ms_out): 0, or a status < 0
+    int read_for(const char* entry, float ms_out[N])
+    {
+        if (!ms_out) {
+            set_error("%s: null argument", entry);
+            return -1;
+        }
+        return std::min(read(ms_out), 0);
     }
 };
 

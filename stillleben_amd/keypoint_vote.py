@@ -20,8 +20,11 @@ from . import _abi, _device, _record_set
 __all__ = ["OUTPUTS", "FLAGS", "KeypointVotes", "make_params", "check_params", "vote", "vote_host"]
 
 NAME = "keypoint_vote"
-OUTPUTS = {"uv": _abi.VOTE_OUT_UV, "n_inliers": _abi.VOTE_OUT_N_INLIERS, "best": _abi.VOTE_OUT_BEST, "flags": _abi.VOTE_OUT_FLAGS,
-           "mean": _abi.VOTE_OUT_MEAN, "cov": _abi.VOTE_OUT_COV, "inliers": _abi.VOTE_OUT_INLIERS}
+_TABLE = (("uv", _abi.VOTE_OUT_UV, (2,), np.float32), ("n_inliers", _abi.VOTE_OUT_N_INLIERS, (), np.int32),
+          ("best", _abi.VOTE_OUT_BEST, (), np.int32), ("flags", _abi.VOTE_OUT_FLAGS, (), np.int32),
+          ("mean", _abi.VOTE_OUT_MEAN, (2,), np.float32), ("cov", _abi.VOTE_OUT_COV, (3,), np.float32),
+          ("inliers", _abi.VOTE_OUT_INLIERS, ("words",), np.uint32))
+OUTPUTS = {name: bit for name, bit, _, _ in _TABLE}
 FLAGS = {"insufficient": _abi.VOTE_INSUFFICIENT, "no_model": _abi.VOTE_NO_MODEL, "refine_stopped": _abi.VOTE_REFINE_STOPPED,
          "refine_rejected": _abi.VOTE_REFINE_REJECTED}
 _ALL = tuple(OUTPUTS)
@@ -51,54 +54,32 @@ def check_params(params):
     return rec
 
 
-def n_words(K):
-    return (int(K) + 31) // 32
+n_words = _record_set.n_words
 
 
-class KeypointVotes:
+class KeypointVotes(_record_set.OutputSet):
     """The position of every keypoint of every set (torch tensors on the device from `vote`, numpy arrays from `vote_host`; those
     not asked for are None):
         uv         float32 [M, Kp, 2] pixel position (pixel index x covers [x, x + 1))     n_inliers  int32 [M, Kp]
         best       int32 [M, Kp] the winning hypothesis (-2: none)                          flags      int32 [M, Kp] bits of FLAGS
         mean, cov  float32 [M, Kp, 2] and [M, Kp, 3] (xx, xy, yy): the hypotheses' weighted mean and covariance
         inliers    uint32 words [M, Kp, ceil(K / 32)] (held as int32 on the device), bit j & 31 of word j >> 5
+        found      bool [M, Kp]: the keypoint has a position
     A keypoint with fewer than 2 valid voters (`insufficient`) or without a hypothesis of min_inliers (`no_model`) has NaN uv,
     mean and cov, 0 inliers, best -2 and no inlier bit -- never a zero position.  `classes`: the class of every set's object
     (SceneBatch.keypoint_votes fills it), what `correspondences` looks the bank up with."""
 
+    NAME, TABLE, RECORD, FAILED = NAME, _TABLE, _abi.KeypointVoteOut, _abi.VOTE_INSUFFICIENT | _abi.VOTE_NO_MODEL
+
     def __init__(self, n_points, uv=None, n_inliers=None, best=None, flags=None, mean=None, cov=None, inliers=None, classes=None):
-        self.n_points = int(n_points)
-        self.uv, self.n_inliers, self.best, self.flags, self.mean, self.cov, self.inliers = uv, n_inliers, best, flags, mean, cov, inliers
-        self.classes = classes
-        self._keepalive = ()
-
-    def __len__(self):
-        for k in _ALL:
-            if getattr(self, k) is not None:
-                return int(getattr(self, k).shape[0])
-        return 0
-
-    @property
-    def found(self):
-        """bool [M, Kp]: the keypoint has a position"""
-        if self.flags is not None:
-            return (self.flags & (_abi.VOTE_INSUFFICIENT | _abi.VOTE_NO_MODEL)) == 0
-        if self.best is not None:
-            return self.best >= 0
-        if self.uv is None:
-            raise RuntimeError("keypoint_vote: `found` reads the `flags`, `best` or `uv` output, and none was asked for")
-        return self.uv[..., 0] == self.uv[..., 0]
+        super().__init__(uv=uv, n_inliers=n_inliers, best=best, flags=flags, mean=mean, cov=cov, inliers=inliers)
+        self.n_points, self.classes = int(n_points), classes
 
     def inlier_mask(self):
         """bool [M, Kp, K]: voter j of a set agrees with the keypoint's position"""
         if self.inliers is None:
             raise RuntimeError("keypoint_vote: the `inliers` output was not asked for")
-        K = self.n_points
-        if isinstance(self.inliers, np.ndarray):
-            j = np.arange(K)
-            return ((self.inliers.view(np.uint32)[..., j >> 5] >> (j & 31).astype(np.uint32)) & 1).astype(bool)
-        j = torch.arange(K, device=self.inliers.device)
-        return ((self.inliers[..., j >> 5] >> (j & 31).to(torch.int32)) & 1).bool()
+        return _record_set.bit_mask(self.inliers, self.n_points)
 
     def cov2x2(self):
         """float32 [M, Kp, 2, 2]: the covariance as a symmetric matrix"""
@@ -133,14 +114,6 @@ class KeypointVotes:
         return self.uv, xyz.contiguous()
 
 
-def _record(ptrs):
-    return _abi.KeypointVoteOut(*(ptrs.get(k) for k in _ALL))
-
-
-_SPEC = (("uv", (2,), np.float32, torch.float32), ("n_inliers", (), np.int32, torch.int32), ("best", (), np.int32, torch.int32),
-         ("flags", (), np.int32, torch.int32), ("mean", (2,), np.float32, torch.float32), ("cov", (3,), np.float32, torch.float32))
-
-
 def _size_of(field, size):
     if size is not None:
         return int(size[0]), int(size[1])
@@ -172,15 +145,11 @@ def vote_host(pixel, field=None, scene=None, vectors=None, size=None, **kw):
     if field is not None and (size[1], size[0]) != vec.shape[1:3]:
         raise ValueError("keypoint_vote: size %r is not the field's" % (size,))
     rec = check_params(make_params(size, M, K, Kp, **kw))
-    mask = int(rec["outputs"][0])
-    outs = {k: np.zeros((M, Kp) + shape, dt) for k, shape, dt, _ in _SPEC if mask & OUTPUTS[k]}
-    if mask & OUTPUTS["inliers"]:
-        outs["inliers"] = np.zeros((M, Kp, n_words(K)), np.uint32)
-    o = _record({k: v.ctypes.data for k, v in outs.items()})
+    res = KeypointVotes(K, **KeypointVotes.empty((M, Kp), int(rec["outputs"][0]), words=n_words(K)))
     st = _abi.lib().slhip_keypoint_vote_host(rec.ctypes.data, pixel.ctypes.data, vec.ctypes.data, None if sc is None else sc.ctypes.data,
-                                             B, C.byref(o))
+                                             B, C.byref(res.record()))
     _abi.check(st, "slhip_keypoint_vote_host")
-    return KeypointVotes(K, **outs)
+    return res
 
 
 def vote(points_or_pixel, field=None, scene=None, vectors=None, size=None, **kw):
@@ -230,11 +199,8 @@ def vote(points_or_pixel, field=None, scene=None, vectors=None, size=None, **kw)
     if field is not None and (size[1], size[0]) != tuple(vec.shape[1:3]):
         raise ValueError("keypoint_vote: size %r is not the field's" % (size,))
     rec = check_params(make_params(size, M, K, Kp, **kw))
-    mask = int(rec["outputs"][0])
-    spec = tuple((k, OUTPUTS[k], (Kp,) + shape, tdt) for k, shape, _, tdt in _SPEC) + (
-        ("inliers", OUTPUTS["inliers"], (Kp, n_words(K)), torch.int32),)
-    res = KeypointVotes(K, **_record_set.empty_outputs(M, mask, dev, spec))
-    out = _record({k: _device.ptr(getattr(res, k)) for k in _ALL})
+    res = KeypointVotes(K, **KeypointVotes.empty((M, Kp), int(rec["outputs"][0]), dev, words=n_words(K)))
+    out = res.record()
     with torch.cuda.device(dev):
         st = _abi.lib().slhip_keypoint_vote(rec.ctypes.data, C.c_void_p(pixel.data_ptr()), C.c_void_p(vec.data_ptr()),
                                             C.c_void_p(_device.ptr(scene)), B, C.byref(out), _device.stream_ptr(dev))

@@ -21,9 +21,11 @@ from . import _abi, _device, _record_set
 __all__ = ["OUTPUTS", "FLAGS", "KeypointVotes3D", "make_params", "check_params", "vote", "vote_host"]
 
 NAME = "keypoint_vote3d"
-OUTPUTS = {"xyz": _abi.VOTE3D_OUT_XYZ, "n_support": _abi.VOTE3D_OUT_N_SUPPORT, "best": _abi.VOTE3D_OUT_BEST,
-           "iters": _abi.VOTE3D_OUT_ITERS, "flags": _abi.VOTE3D_OUT_FLAGS, "mean": _abi.VOTE3D_OUT_MEAN, "cov": _abi.VOTE3D_OUT_COV,
-           "support": _abi.VOTE3D_OUT_SUPPORT}
+_TABLE = (("xyz", _abi.VOTE3D_OUT_XYZ, (3,), np.float32), ("n_support", _abi.VOTE3D_OUT_N_SUPPORT, (), np.int32),
+          ("best", _abi.VOTE3D_OUT_BEST, (), np.int32), ("iters", _abi.VOTE3D_OUT_ITERS, (), np.int32),
+          ("flags", _abi.VOTE3D_OUT_FLAGS, (), np.int32), ("mean", _abi.VOTE3D_OUT_MEAN, (3,), np.float32),
+          ("cov", _abi.VOTE3D_OUT_COV, (6,), np.float32), ("support", _abi.VOTE3D_OUT_SUPPORT, ("words",), np.uint32))
+OUTPUTS = {name: bit for name, bit, _, _ in _TABLE}
 FLAGS = {"insufficient": _abi.VOTE3D_INSUFFICIENT, "no_model": _abi.VOTE3D_NO_MODEL, "not_converged": _abi.VOTE3D_NOT_CONVERGED}
 _ALL = tuple(OUTPUTS)
 
@@ -47,11 +49,10 @@ def check_params(params):
     return rec
 
 
-def n_words(K):
-    return (int(K) + 31) // 32
+n_words = _record_set.n_words
 
 
-class KeypointVotes3D:
+class KeypointVotes3D(_record_set.OutputSet):
     """The position of every keypoint of every set (torch tensors on the device from `vote`, numpy arrays from `vote_host`; those
     not asked for are None):
         xyz        float32 [M, Kp, 3] the winning mode in the camera frame                  n_support  int32 [M, Kp]
@@ -59,45 +60,23 @@ class KeypointVotes3D:
         flags      int32 [M, Kp] bits of FLAGS
         mean, cov  float32 [M, Kp, 3] and [M, Kp, 6] (xx, xy, xz, yy, yz, zz): mean and covariance of the winner's supporters
         support    uint32 words [M, Kp, ceil(K / 32)] (held as int32 on the device), bit j & 31 of word j >> 5
+        found      bool [M, Kp]: the keypoint has a position
     A keypoint without a valid voter (`insufficient`) or without a mode of min_support (`no_model`) has NaN xyz, mean and cov,
     0 supporters, best -2 and no support bit -- never a zero position.  `classes`: the class of every set's object
     (SceneBatch.keypoint_votes3d fills it), what `correspondences` looks the bank up with."""
 
+    NAME, TABLE, RECORD, FAILED = NAME, _TABLE, _abi.KeypointVote3dOut, _abi.VOTE3D_INSUFFICIENT | _abi.VOTE3D_NO_MODEL
+
     def __init__(self, n_points, xyz=None, n_support=None, best=None, iters=None, flags=None, mean=None, cov=None, support=None,
                  classes=None):
-        self.n_points = int(n_points)
-        self.xyz, self.n_support, self.best, self.iters, self.flags = xyz, n_support, best, iters, flags
-        self.mean, self.cov, self.support = mean, cov, support
-        self.classes = classes
-        self._keepalive = ()
-
-    def __len__(self):
-        for k in _ALL:
-            if getattr(self, k) is not None:
-                return int(getattr(self, k).shape[0])
-        return 0
-
-    @property
-    def found(self):
-        """bool [M, Kp]: the keypoint has a position"""
-        if self.flags is not None:
-            return (self.flags & (_abi.VOTE3D_INSUFFICIENT | _abi.VOTE3D_NO_MODEL)) == 0
-        if self.best is not None:
-            return self.best >= 0
-        if self.xyz is None:
-            raise RuntimeError("keypoint_vote3d: `found` reads the `flags`, `best` or `xyz` output, and none was asked for")
-        return self.xyz[..., 0] == self.xyz[..., 0]
+        super().__init__(xyz=xyz, n_support=n_support, best=best, iters=iters, flags=flags, mean=mean, cov=cov, support=support)
+        self.n_points, self.classes = int(n_points), classes
 
     def support_mask(self):
         """bool [M, Kp, K]: voter j of a set supports the keypoint's position"""
         if self.support is None:
             raise RuntimeError("keypoint_vote3d: the `support` output was not asked for")
-        K = self.n_points
-        if isinstance(self.support, np.ndarray):
-            j = np.arange(K)
-            return ((self.support.view(np.uint32)[..., j >> 5] >> (j & 31).astype(np.uint32)) & 1).astype(bool)
-        j = torch.arange(K, device=self.support.device)
-        return ((self.support[..., j >> 5] >> (j & 31).to(torch.int32)) & 1).bool()
+        return _record_set.bit_mask(self.support, self.n_points)
 
     def cov3x3(self):
         """float32 [M, Kp, 3, 3]: the covariance as a symmetric matrix"""
@@ -139,15 +118,6 @@ class KeypointVotes3D:
         return src, dst
 
 
-def _record(ptrs):
-    return _abi.KeypointVote3dOut(*(ptrs.get(k) for k in _ALL))
-
-
-_SPEC = (("xyz", (3,), np.float32, torch.float32), ("n_support", (), np.int32, torch.int32), ("best", (), np.int32, torch.int32),
-         ("iters", (), np.int32, torch.int32), ("flags", (), np.int32, torch.int32), ("mean", (3,), np.float32, torch.float32),
-         ("cov", (6,), np.float32, torch.float32))
-
-
 def vote_host(camera, offsets, **kw):
     """slhip_keypoint_vote3d_host on host arrays: a KeypointVotes3D of numpy arrays.  camera float32 [M, K, 4]; offsets float32
     [M, K, Kp, 3]; `kw`: the other arguments of make_params.  Needs no device: the CPU tests' handle."""
@@ -160,15 +130,11 @@ def vote_host(camera, offsets, **kw):
         raise ValueError("keypoint_vote3d: offsets must be [%d, %d, Kp, 3]" % (M, K))
     Kp = offsets.shape[2]
     rec = check_params(make_params(M, K, Kp, **kw))
-    mask = int(rec["outputs"][0])
-    outs = {k: np.zeros((M, Kp) + shape, dt) for k, shape, dt, _ in _SPEC if mask & OUTPUTS[k]}
-    if mask & OUTPUTS["support"]:
-        outs["support"] = np.zeros((M, Kp, n_words(K)), np.uint32)
-    o = _record({k: v.ctypes.data for k, v in outs.items()})
+    res = KeypointVotes3D(K, **KeypointVotes3D.empty((M, Kp), int(rec["outputs"][0]), words=n_words(K)))
     if M:
-        st = _abi.lib().slhip_keypoint_vote3d_host(rec.ctypes.data, camera.ctypes.data, offsets.ctypes.data, C.byref(o))
+        st = _abi.lib().slhip_keypoint_vote3d_host(rec.ctypes.data, camera.ctypes.data, offsets.ctypes.data, C.byref(res.record()))
         _abi.check(st, "slhip_keypoint_vote3d_host")
-    return KeypointVotes3D(K, **outs)
+    return res
 
 
 def vote(points_or_camera, offsets, **kw):
@@ -195,12 +161,9 @@ def vote(points_or_camera, offsets, **kw):
         raise ValueError("keypoint_vote3d: offsets must be a contiguous float32 [%d, %d, Kp, 3] tensor" % (M, K))
     Kp = int(offsets.shape[2])
     rec = check_params(make_params(M, K, Kp, **kw))
-    mask = int(rec["outputs"][0])
-    spec = tuple((k, OUTPUTS[k], (Kp,) + shape, tdt) for k, shape, _, tdt in _SPEC) + (
-        ("support", OUTPUTS["support"], (Kp, n_words(K)), torch.int32),)
-    res = KeypointVotes3D(K, **_record_set.empty_outputs(M, mask, dev, spec))
+    res = KeypointVotes3D(K, **KeypointVotes3D.empty((M, Kp), int(rec["outputs"][0]), dev, words=n_words(K)))
     if M:
-        out = _record({k: _device.ptr(getattr(res, k)) for k in _ALL})
+        out = res.record()
         with torch.cuda.device(dev):
             st = _abi.lib().slhip_keypoint_vote3d(rec.ctypes.data, C.c_void_p(camera.data_ptr()), C.c_void_p(offsets.data_ptr()),
                                                   C.byref(out), _device.stream_ptr(dev))

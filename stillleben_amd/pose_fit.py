@@ -21,8 +21,27 @@ from . import _abi, _device, _record_set
 __all__ = ["OUTPUTS", "FLAGS", "PoseFit", "make_params", "check_params", "solve", "solve_host"]
 
 NAME = "pose_fit"
-OUTPUTS = {"pose": _abi.FIT_OUT_POSE, "n_used": _abi.FIT_OUT_N_USED, "rms": _abi.FIT_OUT_RMS, "flags": _abi.FIT_OUT_FLAGS}
 FLAGS = {"insufficient": _abi.FIT_INSUFFICIENT, "degenerate": _abi.FIT_DEGENERATE}
+
+
+class PoseFit(_record_set.PoseSet):
+    """The pose of every set (torch tensors on the device from `solve`, numpy arrays from `solve_host`; those not asked for are
+    None):
+        pose    float32 [M, 3, 4] object to camera       n_used  int32 [M] the correspondences that counted
+        rms     float32 [M] root mean square of |R src + t - dst| over them, in the unit of the points
+        flags   int32 [M] bits of FLAGS
+        found   bool [M]: the set has a pose
+    A set with fewer than 3 correspondences that count (`insufficient`) or with collinear or coincident points (`degenerate`)
+    has a NaN pose and rms -- never an identity pose."""
+    NAME, RECORD, FAILED = NAME, _abi.PoseFitOut, _abi.FIT_INSUFFICIENT | _abi.FIT_DEGENERATE
+    TABLE = (("pose", _abi.FIT_OUT_POSE, (3, 4), np.float32), ("n_used", _abi.FIT_OUT_N_USED, (), np.int32),
+             ("rms", _abi.FIT_OUT_RMS, (), np.float32), ("flags", _abi.FIT_OUT_FLAGS, (), np.int32))
+
+    def __init__(self, pose=None, n_used=None, rms=None, flags=None):
+        super().__init__(pose=pose, n_used=n_used, rms=rms, flags=flags)
+
+
+OUTPUTS = PoseFit.OUTPUTS
 _ALL = tuple(OUTPUTS)
 
 
@@ -43,52 +62,6 @@ def check_params(params):
     return rec
 
 
-class PoseFit:
-    """The pose of every set (torch tensors on the device from `solve`, numpy arrays from `solve_host`; those not asked for are
-    None):
-        pose    float32 [M, 3, 4] object to camera       n_used  int32 [M] the correspondences that counted
-        rms     float32 [M] root mean square of |R src + t - dst| over them, in the unit of the points
-        flags   int32 [M] bits of FLAGS
-    A set with fewer than 3 correspondences that count (`insufficient`) or with collinear or coincident points (`degenerate`)
-    has a NaN pose and rms -- never an identity pose."""
-
-    def __init__(self, pose=None, n_used=None, rms=None, flags=None):
-        self.pose, self.n_used, self.rms, self.flags = pose, n_used, rms, flags
-        self._keepalive = ()
-
-    def __len__(self):
-        for k in _ALL:
-            if getattr(self, k) is not None:
-                return int(getattr(self, k).shape[0])
-        return 0
-
-    @property
-    def found(self):
-        """bool [M]: the set has a pose"""
-        if self.flags is not None:
-            return self.flags == 0
-        if self.pose is None:
-            raise RuntimeError("pose_fit: `found` reads the `flags` or `pose` output, and neither was asked for")
-        return self.pose[:, 0, 0] == self.pose[:, 0, 0]
-
-    def dense(self, B, O, scene, slot):
-        """float32 [B, O, 3, 4]: the pose of set i at [scene[i], slot[i] - 1], NaN where a (scene, slot) has no set -- the shape
-        SceneBatch.pose_errors and SceneBatch.pose_vsd take.  `slot` counts from 1 as the renders' instance indices do."""
-        if self.pose is None:
-            raise RuntimeError("pose_fit: the `pose` output was not asked for")
-        if isinstance(self.pose, np.ndarray):
-            out = np.full((int(B), int(O), 3, 4), np.nan, np.float32)
-            out[np.asarray(scene, np.int64), np.asarray(slot, np.int64) - 1] = self.pose
-            return out
-        out = torch.full((int(B), int(O), 3, 4), float("nan"), dtype=torch.float32, device=self.pose.device)
-        out[torch.as_tensor(scene, device=out.device).long(), torch.as_tensor(slot, device=out.device).long() - 1] = self.pose
-        return out
-
-
-def _record(ptrs):
-    return _abi.PoseFitOut(*(ptrs.get(k) for k in _ALL))
-
-
 def solve_host(src, dst, **kw):
     """slhip_pose_fit_host on host arrays: a PoseFit of numpy arrays.  src, dst float32 [M, N, 4]; `kw`: the other arguments of
     make_params.  Needs no device: the CPU tests' handle."""
@@ -98,13 +71,11 @@ def solve_host(src, dst, **kw):
         raise ValueError("pose_fit: src and dst must both be [M, N, 4]")
     M, N = src.shape[:2]
     rec = check_params(make_params(M, N, **kw))
-    mask = int(rec["outputs"][0])
-    spec = (("pose", (M, 3, 4), np.float32), ("n_used", (M,), np.int32), ("rms", (M,), np.float32), ("flags", (M,), np.int32))
-    outs = {k: np.zeros(shape, dt) for k, shape, dt in spec if mask & OUTPUTS[k]}
-    o = _record({k: v.ctypes.data for k, v in outs.items()})
+    res = PoseFit(**PoseFit.empty((M,), int(rec["outputs"][0])))
     if M:
-        _abi.check(_abi.lib().slhip_pose_fit_host(rec.ctypes.data, src.ctypes.data, dst.ctypes.data, C.byref(o)), "slhip_pose_fit_host")
-    return PoseFit(**outs)
+        _abi.check(_abi.lib().slhip_pose_fit_host(rec.ctypes.data, src.ctypes.data, dst.ctypes.data, C.byref(res.record())),
+                   "slhip_pose_fit_host")
+    return res
 
 
 def solve(src, dst, **kw):
@@ -123,15 +94,11 @@ def solve(src, dst, **kw):
     if dst.dtype != torch.float32 or tuple(dst.shape) != (M, N, 4) or not dst.is_contiguous():
         raise ValueError("pose_fit: dst must be a contiguous float32 [%d, %d, 4] tensor" % (M, N))
     rec = check_params(make_params(M, N, **kw))
-    mask = int(rec["outputs"][0])
-    res = PoseFit(**_record_set.empty_outputs(M, mask, dev, (
-        ("pose", _abi.FIT_OUT_POSE, (3, 4), torch.float32), ("n_used", _abi.FIT_OUT_N_USED, (), torch.int32),
-        ("rms", _abi.FIT_OUT_RMS, (), torch.float32), ("flags", _abi.FIT_OUT_FLAGS, (), torch.int32))))
+    res = PoseFit(**PoseFit.empty((M,), int(rec["outputs"][0]), dev))
     if M:
-        out = _record({k: _device.ptr(getattr(res, k)) for k in _ALL})
         with torch.cuda.device(dev):
-            st = _abi.lib().slhip_pose_fit(rec.ctypes.data, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), C.byref(out),
-                                           _device.stream_ptr(dev))
+            st = _abi.lib().slhip_pose_fit(rec.ctypes.data, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()),
+                                           C.byref(res.record()), _device.stream_ptr(dev))
         _abi.check(st, "slhip_pose_fit")
     res._keepalive = (src, dst)      # the launch is asynchronous: its inputs live as long as its outputs
     return res

@@ -25,11 +25,39 @@ from . import pose_error as _pe
 __all__ = ["OUTPUTS", "FLAGS", "FAILED", "PoseICP", "make_params", "check_params", "solve", "solve_host", "surface_points"]
 
 NAME = "pose_icp"
-OUTPUTS = {"pose": _abi.ICP_OUT_POSE, "n_pairs": _abi.ICP_OUT_N_PAIRS, "rms": _abi.ICP_OUT_RMS, "iters": _abi.ICP_OUT_ITERS,
-           "flags": _abi.ICP_OUT_FLAGS, "nearest": _abi.ICP_OUT_NEAREST}
 FLAGS = {"bad_class": _abi.ICP_BAD_CLASS, "no_init": _abi.ICP_NO_INIT, "insufficient": _abi.ICP_INSUFFICIENT,
          "degenerate": _abi.ICP_DEGENERATE, "converged": _abi.ICP_CONVERGED}
 FAILED = _abi.ICP_FAILED      # the failure bits: every flag but `converged`
+
+
+class PoseICP(_record_set.PoseSet):
+    """The refined pose of every set (torch tensors on the device from `solve`, numpy arrays from `solve_host`; those not asked
+    for are None):
+        pose     float32 [M, 3, 4] object to camera       n_pairs  int32 [M] the pairs of the last association
+        rms      float32 [M] root mean square of |R p + t - c| over the pairs of the last fit, in the unit of the points
+        iters    int32 [M] the fits done                   flags    int32 [M] bits of FLAGS
+        nearest  int32 [M, K] the bank point every camera point was paired with in the last association, -1 without a pair
+        found    bool [M]: the set has a pose (no failure bit)
+    A set whose class lies outside the bank (`bad_class`), whose initial pose is not finite (`no_init`), with fewer than
+    min_pairs pairs (`insufficient`) or whose pairs' bank points are collinear or coincident (`degenerate`) has a NaN pose and
+    rms -- never an identity pose, never the initial one.  `converged` is not a failure."""
+    NAME, RECORD, FAILED = NAME, _abi.PoseIcpOut, FAILED
+    TABLE = (("pose", _abi.ICP_OUT_POSE, (3, 4), np.float32), ("n_pairs", _abi.ICP_OUT_N_PAIRS, (), np.int32),
+             ("rms", _abi.ICP_OUT_RMS, (), np.float32), ("iters", _abi.ICP_OUT_ITERS, (), np.int32),
+             ("flags", _abi.ICP_OUT_FLAGS, (), np.int32), ("nearest", _abi.ICP_OUT_NEAREST, ("K",), np.int32))
+
+    def __init__(self, pose=None, n_pairs=None, rms=None, iters=None, flags=None, nearest=None):
+        super().__init__(pose=pose, n_pairs=n_pairs, rms=rms, iters=iters, flags=flags, nearest=nearest)
+
+    @property
+    def converged(self):
+        """bool [M]: the loop ended because the pose stood still"""
+        if self.flags is None:
+            raise RuntimeError("pose_icp: `converged` reads the `flags` output, which was not asked for")
+        return (self.flags & _abi.ICP_CONVERGED) != 0
+
+
+OUTPUTS = PoseICP.OUTPUTS
 _ALL = tuple(OUTPUTS)
 
 
@@ -59,61 +87,6 @@ def check_params(params):
     return rec
 
 
-class PoseICP:
-    """The refined pose of every set (torch tensors on the device from `solve`, numpy arrays from `solve_host`; those not asked
-    for are None):
-        pose     float32 [M, 3, 4] object to camera       n_pairs  int32 [M] the pairs of the last association
-        rms      float32 [M] root mean square of |R p + t - c| over the pairs of the last fit, in the unit of the points
-        iters    int32 [M] the fits done                   flags    int32 [M] bits of FLAGS
-        nearest  int32 [M, K] the bank point every camera point was paired with in the last association, -1 without a pair
-    A set whose class lies outside the bank (`bad_class`), whose initial pose is not finite (`no_init`), with fewer than
-    min_pairs pairs (`insufficient`) or whose pairs' bank points are collinear or coincident (`degenerate`) has a NaN pose and
-    rms -- never an identity pose, never the initial one.  `converged` is not a failure."""
-
-    def __init__(self, pose=None, n_pairs=None, rms=None, iters=None, flags=None, nearest=None):
-        self.pose, self.n_pairs, self.rms, self.iters, self.flags, self.nearest = pose, n_pairs, rms, iters, flags, nearest
-        self._keepalive = ()
-
-    def __len__(self):
-        for k in _ALL:
-            if getattr(self, k) is not None:
-                return int(getattr(self, k).shape[0])
-        return 0
-
-    @property
-    def found(self):
-        """bool [M]: the set has a pose (no failure bit)"""
-        if self.flags is not None:
-            return (self.flags & FAILED) == 0
-        if self.pose is None:
-            raise RuntimeError("pose_icp: `found` reads the `flags` or `pose` output, and neither was asked for")
-        return self.pose[:, 0, 0] == self.pose[:, 0, 0]
-
-    @property
-    def converged(self):
-        """bool [M]: the loop ended because the pose stood still"""
-        if self.flags is None:
-            raise RuntimeError("pose_icp: `converged` reads the `flags` output, which was not asked for")
-        return (self.flags & _abi.ICP_CONVERGED) != 0
-
-    def dense(self, B, O, scene, slot):
-        """float32 [B, O, 3, 4]: the pose of set i at [scene[i], slot[i] - 1], NaN where a (scene, slot) has no set -- the shape
-        SceneBatch.pose_errors and SceneBatch.pose_vsd take.  `slot` counts from 1 as the renders' instance indices do."""
-        if self.pose is None:
-            raise RuntimeError("pose_icp: the `pose` output was not asked for")
-        if isinstance(self.pose, np.ndarray):
-            out = np.full((int(B), int(O), 3, 4), np.nan, np.float32)
-            out[np.asarray(scene, np.int64), np.asarray(slot, np.int64) - 1] = self.pose
-            return out
-        out = torch.full((int(B), int(O), 3, 4), float("nan"), dtype=torch.float32, device=self.pose.device)
-        out[torch.as_tensor(scene, device=out.device).long(), torch.as_tensor(slot, device=out.device).long() - 1] = self.pose
-        return out
-
-
-def _record(ptrs):
-    return _abi.PoseIcpOut(*(ptrs.get(k) for k in _ALL))
-
-
 def solve_host(camera, init, classes, bank, **kw):
     """slhip_pose_icp_host on host arrays: a PoseICP of numpy arrays.  camera float32 [M, K, 4], init float32 [M, 3, 4], classes
     int32 [M], bank = (points float32 [A, N, 4], count int32 [A]); `kw`: the other arguments of make_params.  Needs no device:
@@ -134,15 +107,11 @@ def solve_host(camera, init, classes, bank, **kw):
         raise ValueError("pose_icp: the bank's points must be [A, N, 4]")
     brec, keep = _pe._bank_record(points, count)
     rec = check_params(make_params(M, K, **kw))
-    mask = int(rec["outputs"][0])
-    spec = (("pose", (M, 3, 4), np.float32), ("n_pairs", (M,), np.int32), ("rms", (M,), np.float32), ("iters", (M,), np.int32),
-            ("flags", (M,), np.int32), ("nearest", (M, K), np.int32))
-    outs = {k: np.zeros(shape, dt) for k, shape, dt in spec if mask & OUTPUTS[k]}
-    o = _record({k: v.ctypes.data for k, v in outs.items()})
+    res = PoseICP(**PoseICP.empty((M,), int(rec["outputs"][0]), K=K))
     if M:
         _abi.check(_abi.lib().slhip_pose_icp_host(rec.ctypes.data, camera.ctypes.data, init.ctypes.data, classes.ctypes.data, C.byref(brec),
-                                                  C.byref(o)), "slhip_pose_icp_host")
-    return PoseICP(**outs)
+                                                  C.byref(res.record())), "slhip_pose_icp_host")
+    return res
 
 
 def solve(camera, init, classes, bank, **kw):
@@ -169,13 +138,9 @@ def solve(camera, init, classes, bank, **kw):
     if classes.dtype != torch.int32 or tuple(classes.shape) != (M,) or not classes.is_contiguous():
         raise ValueError("pose_icp: classes must be a contiguous int32 [%d] tensor" % M)
     rec = check_params(make_params(M, K, **kw))
-    mask = int(rec["outputs"][0])
-    res = PoseICP(**_record_set.empty_outputs(M, mask, dev, (
-        ("pose", _abi.ICP_OUT_POSE, (3, 4), torch.float32), ("n_pairs", _abi.ICP_OUT_N_PAIRS, (), torch.int32),
-        ("rms", _abi.ICP_OUT_RMS, (), torch.float32), ("iters", _abi.ICP_OUT_ITERS, (), torch.int32),
-        ("flags", _abi.ICP_OUT_FLAGS, (), torch.int32), ("nearest", _abi.ICP_OUT_NEAREST, (K,), torch.int32))))
+    res = PoseICP(**PoseICP.empty((M,), int(rec["outputs"][0]), dev, K=K))
     if M:
-        out = _record({k: _device.ptr(getattr(res, k)) for k in _ALL})
+        out = res.record()
         brec = bank.record()
         with torch.cuda.device(dev):
             st = _abi.lib().slhip_pose_icp(rec.ctypes.data, C.c_void_p(camera.data_ptr()), C.c_void_p(init.data_ptr()),

@@ -20,10 +20,38 @@ from . import _abi, _device, _record_set
 __all__ = ["OUTPUTS", "FLAGS", "PosePnP", "make_params", "check_params", "solve", "solve_host", "p3p_host"]
 
 NAME = "pose_pnp"
-OUTPUTS = {"pose": _abi.PNP_OUT_POSE, "n_inliers": _abi.PNP_OUT_N_INLIERS, "rms": _abi.PNP_OUT_RMS, "inliers": _abi.PNP_OUT_INLIERS,
-           "best": _abi.PNP_OUT_BEST, "flags": _abi.PNP_OUT_FLAGS}
 FLAGS = {"insufficient": _abi.PNP_INSUFFICIENT, "no_model": _abi.PNP_NO_MODEL, "refine_stopped": _abi.PNP_REFINE_STOPPED,
          "refine_rejected": _abi.PNP_REFINE_REJECTED}
+n_words = _record_set.n_words
+
+
+class PosePnP(_record_set.PoseSet):
+    """The pose of every set (torch tensors on the device from `solve`, numpy arrays from `solve_host`; those not asked for
+    are None):
+        pose       float32 [M, 3, 4] object to camera       n_inliers  int32 [M]
+        rms        float32 [M] reprojection RMS of the inliers in pixels
+        inliers    uint32 words [M, ceil(K / 32)] (held as int32 on the device), bit j & 31 of word j >> 5
+        best       int32 [M] the winning hypothesis (-1: the initial pose, -2: none)
+        flags      int32 [M] bits of FLAGS
+    A set with fewer than 4 valid correspondences (`insufficient`) or without a hypothesis of min_inliers (`no_model`) has a
+    NaN pose, 0 inliers, a NaN rms, best -2 and no inlier bit -- never an identity pose."""
+    NAME, RECORD, FAILED = NAME, _abi.PosePnpOut, _abi.PNP_INSUFFICIENT | _abi.PNP_NO_MODEL
+    TABLE = (("pose", _abi.PNP_OUT_POSE, (3, 4), np.float32), ("n_inliers", _abi.PNP_OUT_N_INLIERS, (), np.int32),
+             ("rms", _abi.PNP_OUT_RMS, (), np.float32), ("inliers", _abi.PNP_OUT_INLIERS, ("words",), np.uint32),
+             ("best", _abi.PNP_OUT_BEST, (), np.int32), ("flags", _abi.PNP_OUT_FLAGS, (), np.int32))
+
+    def __init__(self, n_points, pose=None, n_inliers=None, rms=None, inliers=None, best=None, flags=None):
+        super().__init__(pose=pose, n_inliers=n_inliers, rms=rms, inliers=inliers, best=best, flags=flags)
+        self.n_points = int(n_points)
+
+    def inlier_mask(self):
+        """bool [M, K]: correspondence j of a set is an inlier of its pose"""
+        if self.inliers is None:
+            raise RuntimeError("pose_pnp: the `inliers` output was not asked for")
+        return _record_set.bit_mask(self.inliers, self.n_points)
+
+
+OUTPUTS = PosePnP.OUTPUTS
 _ALL = tuple(OUTPUTS)
 
 
@@ -48,67 +76,6 @@ def check_params(params):
     return rec
 
 
-def n_words(K):
-    return (int(K) + 31) // 32
-
-
-class PosePnP:
-    """The pose of every set (torch tensors on the device from `solve`, numpy arrays from `solve_host`; those not asked for
-    are None):
-        pose       float32 [M, 3, 4] object to camera       n_inliers  int32 [M]
-        rms        float32 [M] reprojection RMS of the inliers in pixels
-        inliers    uint32 words [M, ceil(K / 32)] (held as int32 on the device), bit j & 31 of word j >> 5
-        best       int32 [M] the winning hypothesis (-1: the initial pose, -2: none)
-        flags      int32 [M] bits of FLAGS
-    A set with fewer than 4 valid correspondences (`insufficient`) or without a hypothesis of min_inliers (`no_model`) has a
-    NaN pose, 0 inliers, a NaN rms, best -2 and no inlier bit -- never an identity pose."""
-
-    def __init__(self, n_points, pose=None, n_inliers=None, rms=None, inliers=None, best=None, flags=None):
-        self.n_points = int(n_points)
-        self.pose, self.n_inliers, self.rms, self.inliers, self.best, self.flags = pose, n_inliers, rms, inliers, best, flags
-        self._keepalive = ()
-
-    def __len__(self):
-        for k in _ALL:
-            if getattr(self, k) is not None:
-                return int(getattr(self, k).shape[0])
-        return 0
-
-    def inlier_mask(self):
-        """bool [M, K]: correspondence j of a set is an inlier of its pose"""
-        if self.inliers is None:
-            raise RuntimeError("pose_pnp: the `inliers` output was not asked for")
-        K = self.n_points
-        if isinstance(self.inliers, np.ndarray):
-            j = np.arange(K)
-            return ((self.inliers.view(np.uint32)[:, j >> 5] >> (j & 31).astype(np.uint32)) & 1).astype(bool)
-        j = torch.arange(K, device=self.inliers.device)
-        return ((self.inliers[:, j >> 5] >> (j & 31).to(torch.int32)) & 1).bool()
-
-    def dense(self, B, O, scene, slot):
-        """float32 [B, O, 3, 4]: the pose of set i at [scene[i], slot[i] - 1], NaN where a (scene, slot) has no set -- the shape
-        SceneBatch.pose_errors and SceneBatch.pose_vsd take.  `slot` counts from 1 as the renders' instance indices do."""
-        if self.pose is None:
-            raise RuntimeError("pose_pnp: the `pose` output was not asked for")
-        if isinstance(self.pose, np.ndarray):
-            out = np.full((int(B), int(O), 3, 4), np.nan, np.float32)
-            out[np.asarray(scene, np.int64), np.asarray(slot, np.int64) - 1] = self.pose
-            return out
-        out = torch.full((int(B), int(O), 3, 4), float("nan"), dtype=torch.float32, device=self.pose.device)
-        out[torch.as_tensor(scene, device=out.device).long(), torch.as_tensor(slot, device=out.device).long() - 1] = self.pose
-        return out
-
-
-def _record(ptrs):
-    return _abi.PosePnpOut(*(ptrs.get(k) for k in _ALL))
-
-
-def _host_outputs(M, K, mask):
-    spec = (("pose", (M, 3, 4), np.float32), ("n_inliers", (M,), np.int32), ("rms", (M,), np.float32),
-            ("inliers", (M, n_words(K)), np.uint32), ("best", (M,), np.int32), ("flags", (M,), np.int32))
-    return {k: np.zeros(shape, dt) for k, shape, dt in spec if mask & OUTPUTS[k]}
-
-
 def solve_host(uv, xyz, intrinsics, per_set_intrinsics=None, init=None, **kw):
     """slhip_pose_pnp_host on host arrays: a PosePnP of numpy arrays.  uv [M, K, 2]; xyz [M, K, 4] (point and weight);
     `intrinsics` (fx, fy, cx, cy); per_set_intrinsics [M, 4] or None; init [M, 3, 4] or None; `kw`: the other arguments of
@@ -121,12 +88,11 @@ def solve_host(uv, xyz, intrinsics, per_set_intrinsics=None, init=None, **kw):
     rec = check_params(make_params(intrinsics, M, K, **kw))
     k4 = None if per_set_intrinsics is None else np.ascontiguousarray(per_set_intrinsics, np.float32).reshape(M, 4)
     t0 = None if init is None else np.ascontiguousarray(init, np.float32).reshape(M, 3, 4)
-    outs = _host_outputs(M, K, int(rec["outputs"][0]))
-    o = _record({k: v.ctypes.data for k, v in outs.items()})
+    res = PosePnP(K, **PosePnP.empty((M,), int(rec["outputs"][0]), words=n_words(K)))
     st = _abi.lib().slhip_pose_pnp_host(rec.ctypes.data, uv.ctypes.data, xyz.ctypes.data, None if k4 is None else k4.ctypes.data,
-                                        None if t0 is None else t0.ctypes.data, C.byref(o))
+                                        None if t0 is None else t0.ctypes.data, C.byref(res.record()))
     _abi.check(st, "slhip_pose_pnp_host")
-    return PosePnP(K, **outs)
+    return res
 
 
 def p3p_host(uv, xyz, intrinsics):
@@ -184,12 +150,8 @@ def solve(uv, xyz=None, intrinsics=None, per_set_intrinsics=None, init=None, coo
     if init is not None and (init.dtype != torch.float32 or tuple(init.shape) != (M, 3, 4) or not init.is_contiguous()):
         raise ValueError("pose_pnp: init must be a contiguous float32 [%d, 3, 4] tensor" % M)
     rec = check_params(make_params(intrinsics, M, K, **kw))
-    mask = int(rec["outputs"][0])
-    res = PosePnP(K, **_record_set.empty_outputs(M, mask, dev, (
-        ("pose", _abi.PNP_OUT_POSE, (3, 4), torch.float32), ("n_inliers", _abi.PNP_OUT_N_INLIERS, (), torch.int32),
-        ("rms", _abi.PNP_OUT_RMS, (), torch.float32), ("inliers", _abi.PNP_OUT_INLIERS, (n_words(K),), torch.int32),
-        ("best", _abi.PNP_OUT_BEST, (), torch.int32), ("flags", _abi.PNP_OUT_FLAGS, (), torch.int32))))
-    out = _record({k: _device.ptr(getattr(res, k)) for k in _ALL})
+    res = PosePnP(K, **PosePnP.empty((M,), int(rec["outputs"][0]), dev, words=n_words(K)))
+    out = res.record()
     with torch.cuda.device(dev):
         st = _abi.lib().slhip_pose_pnp(rec.ctypes.data, C.c_void_p(uv.data_ptr()), C.c_void_p(xyz.data_ptr()),
                                        C.c_void_p(_device.ptr(per_set_intrinsics)), C.c_void_p(_device.ptr(init)), C.byref(out),

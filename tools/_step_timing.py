@@ -1,16 +1,18 @@
-"""The scaffold of tools/time_object_{crops,points,keypoints,regions}.py: repeated calls under the HIP events of
-slhip_object_<what>_timing_enable, read out with slhip_object_<what>_timings after every call."""
+"""The scaffold of the tools/time_*.py that read a module's step timers: repeated calls under the HIP events of
+slhip_<entry>_timing_enable, read out with slhip_<entry>_timings after every call.  `entry` is the stem of the two names, such
+as "object_crops" or "pose_icp"."""
 import ctypes as C
+import statistics
 
 from stillleben_amd import _abi
 
 
-def timed(what, steps, fn, rep, warm=2):
-    """fn() warm + rep times with the step timers of object_<what> on (the warm-up calls: code objects, allocator).  Returns
+def timed(entry, steps, fn, rep, warm=2):
+    """fn() warm + rep times with the step timers of `entry` on (the warm-up calls: code objects, allocator).  Returns
     (the last result, the `steps` milliseconds of each of the last `rep` calls as tuples; -1.0 or an error for a step that fn
     does not run, as the module's read-out has it)."""
     L = _abi.lib()
-    enable, read = "slhip_object_%s_timing_enable" % what, "slhip_object_%s_timings" % what
+    enable, read = "slhip_%s_timing_enable" % entry, "slhip_%s_timings" % entry
     _abi.check(getattr(L, enable)(1), enable)
     out, times = None, []
     for r in range(warm + rep):
@@ -21,3 +23,10 @@ def timed(what, steps, fn, rep, warm=2):
             times.append(tuple(ms))
     _abi.check(getattr(L, enable)(0), enable)
     return out, times
+
+
+def timed_step(entry, steps, which, fn, rep, warm=2):
+    """timed() for step `which` alone: (the last result, its median ms, its ms of every call)"""
+    out, times = timed(entry, steps, fn, rep, warm)
+    ms = [t[which] for t in times]
+    return out, statistics.median(ms), ms

@@ -8,7 +8,6 @@ and the torch formulation of the same step (pairs, meeting points, the [m, Kp, H
 slice of 32 sets, the most whose intermediates fit comfortably, timed with torch's events and scaled to M sets.  The sets are made on
 the device from a seed; the tool reads nothing outside the repository.  Prints one JSON line per shape.
     python tools/time_keypoint_vote.py [repeats=10] [sets=2048]"""
-import ctypes as C
 import json
 import os
 import statistics
@@ -23,6 +22,8 @@ import stillleben_amd as sl  # noqa: E402
 from stillleben_amd import _abi  # noqa: E402
 from stillleben_amd import keypoint_vote as kv  # noqa: E402
 
+import _step_timing  # noqa: E402
+
 REP = max(3, int(sys.argv[1]) if len(sys.argv) > 1 else 10)
 M = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 KP, HY, SIZE, SCENES, SLICE = 9, 128, (640, 480), 16, 32
@@ -31,21 +32,10 @@ sl.init_cuda(0)
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev)
 g.manual_seed(20261020)
-L = _abi.lib()
 
 
 def timed(fn, which, rep=REP, warm=2):
-    """fn() warm + rep times under the entry's own events: (last result, median ms, all ms)"""
-    _abi.check(L.slhip_keypoint_vote_timing_enable(1), "slhip_keypoint_vote_timing_enable")
-    out, ms = None, []
-    for r in range(warm + rep):
-        out = fn()
-        t = (C.c_float * 2)()
-        _abi.check(L.slhip_keypoint_vote_timings(C.byref(t)), "slhip_keypoint_vote_timings")
-        if r >= warm:
-            ms.append(t[which])
-    _abi.check(L.slhip_keypoint_vote_timing_enable(0), "slhip_keypoint_vote_timing_enable")
-    return out, statistics.median(ms), ms
+    return _step_timing.timed_step("keypoint_vote", 2, which, fn, rep, warm)
 
 
 def sets(K):

@@ -8,7 +8,6 @@ per iteration, every seed stepped until all have stopped -- on a slice of 32 set
 timed with torch's events and scaled to M sets; then the rigid fit (slhip_pose_fit) of the voted keypoints onto the true ones.
 The sets are made on the device from a seed; the tool reads nothing outside the repository.  Prints one JSON line per shape.
     python tools/time_keypoint_vote3d.py [repeats=10] [sets=1280]"""
-import ctypes as C
 import json
 import os
 import statistics
@@ -24,6 +23,8 @@ from stillleben_amd import _abi  # noqa: E402
 from stillleben_amd import keypoint_vote3d as kv  # noqa: E402
 from stillleben_amd import pose_fit as pf  # noqa: E402
 
+import _step_timing  # noqa: E402
+
 REP = max(3, int(sys.argv[1]) if len(sys.argv) > 1 else 10)
 M = int(sys.argv[2]) if len(sys.argv) > 2 else 1280
 KP, K, S, H, TOL, ITERS, SLICE = 9, 1024, 128, 0.05, 1e-4, 32, 32
@@ -31,21 +32,10 @@ sl.init_cuda(0)
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev)
 g.manual_seed(20261020)
-L = _abi.lib()
 
 
-def timed(fn, enable, read, rep=REP, warm=2):
-    """fn() warm + rep times under the entry's own events: (last result, median ms, all ms)"""
-    _abi.check(enable(1), "timing_enable")
-    out, ms = None, []
-    for r in range(warm + rep):
-        out = fn()
-        t = (C.c_float * 1)()
-        _abi.check(read(C.byref(t)), "timings")
-        if r >= warm:
-            ms.append(t[0])
-    _abi.check(enable(0), "timing_enable")
-    return out, statistics.median(ms), ms
+def timed(fn, entry, rep=REP, warm=2):
+    return _step_timing.timed_step(entry, 1, 0, fn, rep, warm)
 
 
 def sets():
@@ -84,7 +74,7 @@ def torch_vote(cam, off):
 
 cam, off, kps = sets()
 kw = dict(n_seeds=S, bandwidth=H, tol=TOL, max_iters=ITERS)
-res, ms, all_ms = timed(lambda: kv.vote(cam, off, **kw), L.slhip_keypoint_vote3d_timing_enable, L.slhip_keypoint_vote3d_timings)
+res, ms, all_ms = timed(lambda: kv.vote(cam, off, **kw), "keypoint_vote3d")
 torch.cuda.synchronize()
 print(json.dumps({"shape": "vote3d_M%d_Kp%d_K%d_S%d" % (M, KP, K, S), "ms": round(ms, 4), "ms_min_max": [round(min(all_ms), 4), round(max(all_ms), 4)],
                   "repeats": REP, "found": int(res.found.sum()), "of": M * KP, "median_support": int(res.n_support.median()),
@@ -110,11 +100,11 @@ print(json.dumps({"shape": "torch_M%d_Kp%d_K%d_S%d" % (SLICE, KP, K, S), "ms": r
 src = torch.ones((M, KP, 4), device=dev)
 src[..., :3] = (torch.rand((1, KP, 3), generator=g, device=dev) - 0.5) * 0.25
 dst = torch.cat([res.xyz, res.found.float()[..., None]], -1).contiguous()
-fit, ms, all_ms = timed(lambda: pf.solve(src, dst), L.slhip_pose_fit_timing_enable, L.slhip_pose_fit_timings)
+fit, ms, all_ms = timed(lambda: pf.solve(src, dst), "pose_fit")
 torch.cuda.synchronize()
 print(json.dumps({"shape": "fit_M%d_N%d" % (M, KP), "ms": round(ms, 4), "ms_min_max": [round(min(all_ms), 4), round(max(all_ms), 4)], "repeats": REP}))
 big_src = torch.ones((M, K, 4), device=dev)
 big_src[..., :3] = torch.rand((M, K, 3), generator=g, device=dev) - 0.5
-fit, ms, all_ms = timed(lambda: pf.solve(big_src, cam), L.slhip_pose_fit_timing_enable, L.slhip_pose_fit_timings)
+fit, ms, all_ms = timed(lambda: pf.solve(big_src, cam), "pose_fit")
 torch.cuda.synchronize()
 print(json.dumps({"shape": "fit_M%d_N%d" % (M, K), "ms": round(ms, 4), "ms_min_max": [round(min(all_ms), 4), round(max(all_ms), 4)], "repeats": REP}))

@@ -86,7 +86,7 @@ buffers.coord = torch.rand((B, H, W, 4), generator=g, device=dev)
 buffers.normals, buffers.instance = None, inst.view(B, H, W, 1)
 buffers.object_stats, buffers.object_masks = stats, masks
 
-crops, times = _step_timing.timed("crops", 2, lambda: oc.extract(buffers, K, **KW), REP)
+crops, times = _step_timing.timed("object_crops", 2, lambda: oc.extract(buffers, K, **KW), REP)
 n = len(crops)
 bx0, by0, side = (crops.box[:, k].double() for k in (0, 1, 2))
 area = ((bx0 + side).clamp(0, W) - bx0.clamp(0, W)) * ((by0 + side).clamp(0, H) - by0.clamp(0, H))      # the part inside the picture

@@ -37,9 +37,7 @@ dev = torch.device("cuda", 0)
 
 
 def timed(fn, which, warm=2):
-    out, times = _step_timing.timed("keypoints", 3, fn, REP, warm)
-    ms = [t[which] for t in times]
-    return out, statistics.median(ms), ms
+    return _step_timing.timed_step("object_keypoints", 3, which, fn, REP, warm)
 
 
 # ---- fps

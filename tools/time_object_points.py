@@ -74,7 +74,7 @@ buffers.coord = torch.rand((B, H, W, 4), generator=g, device=dev) + 0.5
 buffers.rgb, buffers.normals, buffers.instance = None, None, inst.view(B, H, W, 1)
 buffers.object_stats, buffers.object_masks = stats, masks
 
-points, times = _step_timing.timed("points", 2, lambda: op.extract(buffers, K4, **KW), REP)
+points, times = _step_timing.timed("object_points", 2, lambda: op.extract(buffers, K4, **KW), REP)
 n = len(points)
 # every point is a visible pixel of its object
 hit = inst[points.scene.long()[:, None], points.pixel[..., 1].long(), points.pixel[..., 0].long()] == points.slot[:, None]

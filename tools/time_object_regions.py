@@ -32,9 +32,7 @@ dev = torch.device("cuda", 0)
 
 
 def timed(fn, which, warm=3):
-    out, times = _step_timing.timed("regions", 3, fn, REP, warm)
-    ms = [t[which] for t in times]
-    return out, statistics.median(ms), ms
+    return _step_timing.timed_step("object_regions", 3, which, fn, REP, warm)
 
 
 table = sl.AssetTable(synthetic.ycb_like_meshes(seed=0, tex_size=64))

@@ -10,7 +10,6 @@ and beside each the plain-torch formulation of the same quantities a user would 
 inputs: torch.cdist in chunks of pose pairs that fit memory for ADD-S, a [chunk, S, N] distance tensor for MSSD and MSPD.  The
 bank and the poses are made on the device from a seed.  Prints one JSON line.
     python tools/time_pose_error.py [repeats=10] [scenes=1024] [torch_repeats=2]"""
-import ctypes as C
 import json
 import os
 import statistics
@@ -23,8 +22,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import stillleben_amd as sl  # noqa: E402
-from stillleben_amd import _abi  # noqa: E402
 from stillleben_amd import pose_error as pe  # noqa: E402
+
+import _step_timing  # noqa: E402
 
 REP = max(3, int(sys.argv[1]) if len(sys.argv) > 1 else 10)
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
@@ -35,21 +35,10 @@ sl.init_cuda(0)
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev)
 g.manual_seed(20261019)
-L = _abi.lib()
 
 
 def timed(fn, which, rep=REP, warm=2):
-    """fn() warm + rep times under the entry's own events: (last result, median ms, all ms)"""
-    _abi.check(L.slhip_pose_error_timing_enable(1), "slhip_pose_error_timing_enable")
-    out, ms = None, []
-    for r in range(warm + rep):
-        out = fn()
-        t = (C.c_float * 2)()
-        _abi.check(L.slhip_pose_error_timings(C.byref(t)), "slhip_pose_error_timings")
-        if r >= warm:
-            ms.append(t[which])
-    _abi.check(L.slhip_pose_error_timing_enable(0), "slhip_pose_error_timing_enable")
-    return out, statistics.median(ms), ms
+    return _step_timing.timed_step("pose_error", 2, which, fn, rep, warm)
 
 
 def torch_timed(fn, rep=TORCH_REP):

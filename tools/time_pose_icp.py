@@ -9,11 +9,9 @@ shifted by 5 mm.  The cost model of DESIGN.md "ICP" -- K * count dist2 evaluatio
 every measurement as evaluations per second.  The tool reads nothing outside the repository and ends after one pass.
 Prints one JSON line per shape.
     python tools/time_pose_icp.py [repeats=5]"""
-import ctypes as C
 import json
 import math
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,8 +20,9 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import stillleben_amd as sl  # noqa: E402
-from stillleben_amd import _abi  # noqa: E402
 from stillleben_amd import pose_icp as pi  # noqa: E402
+
+import _step_timing  # noqa: E402
 
 REP = max(3, int(sys.argv[1]) if len(sys.argv) > 1 else 5)
 A, ITERS = 8, 5
@@ -31,21 +30,10 @@ sl.init_cuda(0)
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev)
 g.manual_seed(20261021)
-L = _abi.lib()
 
 
 def timed(fn, rep=REP, warm=1):
-    """fn() warm + rep times under the entry's own events: (last result, median ms, all ms)"""
-    _abi.check(L.slhip_pose_icp_timing_enable(1), "timing_enable")
-    out, ms = None, []
-    for r in range(warm + rep):
-        out = fn()
-        t = (C.c_float * 1)()
-        _abi.check(L.slhip_pose_icp_timings(C.byref(t)), "timings")
-        if r >= warm:
-            ms.append(t[0])
-    _abi.check(L.slhip_pose_icp_timing_enable(0), "timing_enable")
-    return out, statistics.median(ms), ms
+    return _step_timing.timed_step("pose_icp", 1, 0, fn, rep, warm)
 
 
 def rotations(n, max_angle):

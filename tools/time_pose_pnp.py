@@ -8,10 +8,8 @@ errors" table in DESIGN.md: M * Hy * K point tests of SCORE_VALU instructions ea
 "Pose PnP"), one instruction per lane and cycle on 256 CUs x 4 SIMDs x 16 lanes at 2.4 GHz.  The sets are made on the device from
 a seed; the tool reads nothing outside the repository.  Prints one JSON line per shape.
     python tools/time_pose_pnp.py [repeats=10] [sets=2048]"""
-import ctypes as C
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,8 +18,9 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import stillleben_amd as sl  # noqa: E402
-from stillleben_amd import _abi  # noqa: E402
 from stillleben_amd import pose_pnp as pnp  # noqa: E402
+
+import _step_timing  # noqa: E402
 
 REP = max(3, int(sys.argv[1]) if len(sys.argv) > 1 else 10)
 M = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
@@ -32,21 +31,10 @@ sl.init_cuda(0)
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev)
 g.manual_seed(20261020)
-L = _abi.lib()
 
 
 def timed(fn, which, rep=REP, warm=2):
-    """fn() warm + rep times under the entry's own events: (last result, median ms, all ms)"""
-    _abi.check(L.slhip_pose_pnp_timing_enable(1), "slhip_pose_pnp_timing_enable")
-    out, ms = None, []
-    for r in range(warm + rep):
-        out = fn()
-        t = (C.c_float * 2)()
-        _abi.check(L.slhip_pose_pnp_timings(C.byref(t)), "slhip_pose_pnp_timings")
-        if r >= warm:
-            ms.append(t[which])
-    _abi.check(L.slhip_pose_pnp_timing_enable(0), "slhip_pose_pnp_timing_enable")
-    return out, statistics.median(ms), ms
+    return _step_timing.timed_step("pose_pnp", 2, which, fn, rep, warm)
 
 
 def poses(n):

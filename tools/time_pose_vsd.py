@@ -55,7 +55,8 @@ import torch  # noqa: E402
 
 import stillleben_amd as sl  # noqa: E402
 from stillleben_amd import pose_vsd as pv  # noqa: E402
-from stillleben_amd import _abi  # noqa: E402
+
+import _step_timing  # noqa: E402
 
 REP = max(3, int(sys.argv[1]) if len(sys.argv) > 1 else 10)
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
@@ -68,20 +69,7 @@ g.manual_seed(20261020)
 
 
 def timed(fn, rep, warm=2):
-    """fn() warm + rep times under the entries' own events: (last result, the two milliseconds of each of the last `rep` calls)"""
-    import ctypes as C
-
-    L = _abi.lib()
-    _abi.check(L.slhip_pose_vsd_timing_enable(1), "slhip_pose_vsd_timing_enable")
-    out, times = None, []
-    for r in range(warm + rep):
-        out = fn()
-        ms = (C.c_float * 2)()
-        _abi.check(L.slhip_pose_vsd_timings(C.byref(ms)), "slhip_pose_vsd_timings")
-        if r >= warm:
-            times.append(tuple(ms))
-    _abi.check(L.slhip_pose_vsd_timing_enable(0), "slhip_pose_vsd_timing_enable")
-    return out, times
+    return _step_timing.timed("pose_vsd", 2, fn, rep, warm)
 
 
 def icosphere(levels):

@@ -1615,6 +1615,92 @@ int slhip_pose_fit_timing_enable(int on);
 int slhip_pose_fit_timings(float ms_out[1]);
 
 /* ---------------------------------------------------------------------------------------------
+ * Robust alignment: the pose (object to camera) of every set of K 3D-3D correspondences that has the
+ * most inliers, refitted on them -- RANSAC round the rigid fit above, for predicted object coordinates
+ * or voted keypoints of which some are wrong by the size of the object (slhip_pose_fit is plain least
+ * squares and is ruined by one of them).  This project's addition.  All float32, one rounded IEEE
+ * operation at a time, only + - * / sqrt fabs and comparisons; csrc/slhip_align_rules.h holds the rules
+ * for host and device, so slhip_pose_align_host gives the device's outputs bit for bit.  DESIGN.md
+ * "Robust alignment" states them operation by operation; in short, per set:
+ *   1. valid list: correspondence j counts by rule 1 of "Rigid fit" (src.w > 0, dst.w != 0, the six
+ *      coordinates finite); the valid ones are taken in ascending j, n_valid of them; fewer than 3:
+ *      SLHIP_ALIGN_INSUFFICIENT.
+ *   2. hypothesis h draws Philox counter (set_id_base + set, 9, h, 0x51DE5EED) under (seed_lo, seed_hi)
+ *      ("Randomness" below); words 0, 1, 2 each pick min(n_valid - 1, (uint32_t)(uniform(x) *
+ *      (float)n_valid)) of the valid list; two equal picks: void.
+ *   3. rules 2 to 6 of "Rigid fit" on the three pairs: centroids ((p0 + p1) + p2) / 3.0f, the nine moments
+ *      (a0_i*b0_j + a1_i*b1_j) + a2_i*b2_j of the centred pairs, Horn's matrix, 8 Jacobi sweeps, the
+ *      quaternion and min_gap.  A degenerate sample (collinear or coincident) or a pose entry that is
+ *      not finite: void.
+ *   4. score = the number of valid correspondences with |R s + t - d|^2 <= threshold * threshold, the
+ *      residual of rule 7 of "Rigid fit"; a NaN compares false, a void hypothesis scores 0.  Slot 0 is
+ *      d_init (not finite: scores 0), slot h + 1 hypothesis h; the winner is the arg-max of (count << 13) |
+ *      (4097 - slot): highest score, ties to the lowest slot, so d_init (index -1) wins ties.  A winner
+ *      below min_inliers: SLHIP_ALIGN_NO_MODEL.
+ *   5. refine_iters times: the inliers of the current pose among the valid list, then rules 2 to 6 of
+ *      "Rigid fit" on them, lanes over the list index i (lane i % 256 upwards, the butterfly, ((w0 + w1) +
+ *      w2) + w3).  Fewer than 3 inliers or a degenerate fit: SLHIP_ALIGN_REFINE_STOPPED, the pose stays
+ *      and the loop ends.
+ *   6. inliers, count and rms = sqrtf(sum of squared residuals / (float)count) of the refitted pose over
+ *      the correspondences j in their own order (lane j % 256); fewer inliers than the winner's score:
+ *      the winner's pose and figures with SLHIP_ALIGN_REFINE_REJECTED.
+ * INSUFFICIENT and NO_MODEL give a NaN pose, 0 inliers, NaN rms, best -2 and zero bits -- never an
+ * identity pose and never d_init.  Rigid motions only: a similarity scale (Umeyama) is not estimated.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_ALIGN_POINTS_MAX      4096u
+#define SLHIP_ALIGN_HYPOTHESES_MAX  4096u
+#define SLHIP_ALIGN_REFINE_MAX      16u
+#define SLHIP_ALIGN_OUT_POSE      1u
+#define SLHIP_ALIGN_OUT_N_INLIERS 2u
+#define SLHIP_ALIGN_OUT_RMS       4u
+#define SLHIP_ALIGN_OUT_INLIERS   8u
+#define SLHIP_ALIGN_OUT_BEST      16u
+#define SLHIP_ALIGN_OUT_FLAGS     32u
+#define SLHIP_ALIGN_INSUFFICIENT    1      /* flags: fewer than 3 valid correspondences                        */
+#define SLHIP_ALIGN_NO_MODEL        2      /* flags: no hypothesis reached min_inliers                         */
+#define SLHIP_ALIGN_REFINE_STOPPED  4      /* flags: a refit had fewer than 3 inliers or was degenerate        */
+#define SLHIP_ALIGN_REFINE_REJECTED 8      /* flags: the refitted pose held fewer inliers; the winner is returned */
+
+typedef struct {
+    uint32_t n_sets;           /* M                                                                           */
+    uint32_t n_points;         /* K, 3..SLHIP_ALIGN_POINTS_MAX                                                */
+    uint32_t n_hypotheses;     /* Hy, 0..SLHIP_ALIGN_HYPOTHESES_MAX; 0 needs d_init (a pure refit)            */
+    float threshold;           /* inlier threshold in the unit of the points, > 0 and finite                  */
+    float min_gap;             /* in [0, 1): rule 6 of "Rigid fit", for the samples and the refits            */
+    uint32_t refine_iters;     /* 0..SLHIP_ALIGN_REFINE_MAX                                                   */
+    uint32_t min_inliers;      /* >= 3                                                                        */
+    uint32_t seed_lo, seed_hi; /* Philox key                                                                  */
+    uint32_t set_id_base;      /* set i draws as set_id_base + i                                              */
+    uint32_t outputs;          /* SLHIP_ALIGN_OUT_* bits, at least one                                        */
+    uint32_t _pad[5];
+} slhip_pose_align_params; /* 64 bytes */
+
+typedef struct {               /* read only when its bit is set; every pointer 4-byte aligned                 */
+    float* pose;               /* f32 [M, 3, 4], object to camera                                             */
+    int32_t* n_inliers;        /* i32 [M]                                                                     */
+    float* rms;                /* f32 [M], RMS of |R src + t - dst| over the inliers, in the unit of the points */
+    uint32_t* inliers;         /* u32 [M, ceil(K / 32)], bit j & 31 of word j >> 5                            */
+    int32_t* best;             /* i32 [M], the winning hypothesis; -1: d_init; -2: none                       */
+    int32_t* flags;            /* i32 [M], SLHIP_ALIGN_* flag bits                                            */
+} slhip_pose_align_out;
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_pose_align_check_params(const slhip_pose_align_params* params);
+/* d_src f32 [M, K, 4] object frame, d_dst f32 [M, K, 4] camera frame, both 16-byte aligned (the layouts of slhip_pose_fit);
+ * d_init NULL or f32 [M, 3, 4], 4-byte aligned: a pose that competes as index -1 and wins ties.  Every output named in
+ * params->outputs is written exactly once per set, the others are not touched.  n_sets == 0 does nothing; null pointers (an
+ * output named in the mask included), misalignment, Hy == 0 without d_init and bad parameters are refused before anything
+ * touches the device.  One workgroup per set, the valid list in 24 * K bytes of LDS.  Asynchronous on `stream`.          */
+int slhip_pose_align(const slhip_pose_align_params* params, const float* d_src, const float* d_dst, const float* d_init,
+                     const slhip_pose_align_out* out, void* stream);
+/* The same rules on host arrays through csrc/slhip_align_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_pose_align_host(const slhip_pose_align_params* params, const float* h_src, const float* h_dst, const float* h_init,
+                          const slhip_pose_align_out* out);
+/* Developer hook (tools/time_pose_align.py): HIP events round the last slhip_pose_align [0] (-1: not run). */
+int slhip_pose_align_timing_enable(int on);
+int slhip_pose_align_timings(float ms_out[1]);
+
+/* ---------------------------------------------------------------------------------------------
  * ICP: the pose (object to camera) of every set of K camera points refined against the points of its
  * class in a slhip_pose_bank, point to point, from an initial pose -- the refinement step of DenseFusion,
  * PVN3D, FFB6D, PoseCNN+ICP and the BOP baselines.  This project's addition.  The loop round two rules
@@ -1762,6 +1848,9 @@ int slhip_stream_destroy(void* stream);
  * Stream 8, voter samples (slhip_keypoint_vote only; its key and set id base are the caller's, the set id stands where the
  * scene id does, and the keypoint k stands where 0x51DE5EED does): index = the hypothesis h, x[0] and x[1] pick the two voters
  * whose lines are intersected, each by the pick rule above over the n_valid voters ("Keypoint voting" above).
+ * Stream 9, alignment samples (slhip_pose_align only; its key and set id base are the caller's, the set id stands where the
+ * scene id does): index = the hypothesis h, x[0], x[1], x[2] pick the three correspondences of the minimal sample, each by the
+ * pick rule above over the n_valid correspondences ("Robust alignment" above); x[3] is not used.
  * Views (slhip_synth_place_view): azimuth and elevation of view v >= 1 are the draw of view 0 -- stream 0, index 0, words 1 and
  * 2, the same scene id, the same formulas -- under the key (seed_lo + v * 0x9E3779B9, seed_hi + v * 0xBB67AE85), each sum
  * wrapping at 32 bits.  No other draw uses the view's key: the light's normals, the environment's gates and picks and everything

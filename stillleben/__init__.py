@@ -17,6 +17,7 @@ from stillleben_amd import pose_pnp, PosePnP  # noqa: F401  (additive: the pose 
 from stillleben_amd import keypoint_vote, KeypointVotes  # noqa: F401  (additive: predicted vector fields to 2D keypoints)
 from stillleben_amd import keypoint_vote3d, KeypointVotes3D  # noqa: F401  (additive: predicted 3D offsets to camera-frame keypoints)
 from stillleben_amd import pose_fit, PoseFit  # noqa: F401  (additive: the pose of every set of 3D-3D correspondences)
+from stillleben_amd import pose_align, PoseAlign  # noqa: F401  (additive: the robust pose of every set of 3D-3D correspondences)
 from stillleben_amd import pose_icp, PoseICP  # noqa: F401  (additive: ICP refinement of a pose against the depth's camera points)
 
 __all__ = _impl.__all__

@@ -46,6 +46,8 @@ from . import keypoint_vote3d  # noqa: F401  (additive: predicted 3D offsets to 
 from .keypoint_vote3d import KeypointVotes3D  # noqa: F401
 from . import pose_fit  # noqa: F401  (additive: the pose of every set of 3D-3D correspondences, Horn's closed form)
 from .pose_fit import PoseFit  # noqa: F401
+from . import pose_align  # noqa: F401  (additive: the pose of every set of 3D-3D correspondences with the most inliers, RANSAC round Horn's fit)
+from .pose_align import PoseAlign  # noqa: F401
 from . import pose_icp  # noqa: F401  (additive: ICP refinement of a pose against the depth's camera points, on a model bank)
 from .pose_icp import PoseICP  # noqa: F401
 
@@ -62,6 +64,7 @@ __all__ = [
     'keypoint_vote', 'KeypointVotes',
     'keypoint_vote3d', 'KeypointVotes3D',
     'pose_fit', 'PoseFit',
+    'pose_align', 'PoseAlign',
     'pose_icp', 'PoseICP',
 ]
 

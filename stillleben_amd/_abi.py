@@ -68,6 +68,9 @@ VOTE3D_INSUFFICIENT, VOTE3D_NO_MODEL, VOTE3D_NOT_CONVERGED = 1, 2, 4            
 FIT_POINTS_MAX = 4096                                                            # SLHIP_FIT_POINTS_MAX
 FIT_OUT_POSE, FIT_OUT_N_USED, FIT_OUT_RMS, FIT_OUT_FLAGS = 1, 2, 4, 8            # SLHIP_FIT_OUT_*
 FIT_INSUFFICIENT, FIT_DEGENERATE = 1, 2                                          # SLHIP_FIT_*: the flag bits of a set
+ALIGN_POINTS_MAX, ALIGN_HYPOTHESES_MAX, ALIGN_REFINE_MAX = 4096, 4096, 16       # SLHIP_ALIGN_*_MAX
+ALIGN_OUT_POSE, ALIGN_OUT_N_INLIERS, ALIGN_OUT_RMS, ALIGN_OUT_INLIERS, ALIGN_OUT_BEST, ALIGN_OUT_FLAGS = 1, 2, 4, 8, 16, 32      # SLHIP_ALIGN_OUT_*
+ALIGN_INSUFFICIENT, ALIGN_NO_MODEL, ALIGN_REFINE_STOPPED, ALIGN_REFINE_REJECTED = 1, 2, 4, 8      # SLHIP_ALIGN_*: the flag bits of a set
 ICP_POINTS_MAX, ICP_ITERS_MAX = 4096, 64                                         # SLHIP_ICP_POINTS_MAX, SLHIP_ICP_ITERS_MAX
 ICP_OUT_POSE, ICP_OUT_N_PAIRS, ICP_OUT_RMS, ICP_OUT_ITERS, ICP_OUT_FLAGS, ICP_OUT_NEAREST = 1, 2, 4, 8, 16, 32      # SLHIP_ICP_OUT_*
 ICP_BAD_CLASS, ICP_NO_INIT, ICP_INSUFFICIENT, ICP_DEGENERATE, ICP_CONVERGED = 1, 2, 4, 8, 16      # SLHIP_ICP_*: the flag bits of a set
@@ -412,6 +415,22 @@ class PoseFitOut(C.Structure):
     _fields_ = [("pose", C.c_void_p), ("n_used", C.c_void_p), ("rms", C.c_void_p), ("flags", C.c_void_p)]
 
 
+# slhip_pose_align_params (include/slhip.h), 64 bytes
+POSE_ALIGN_PARAMS_DTYPE = np.dtype([
+    ("n_sets", np.uint32), ("n_points", np.uint32), ("n_hypotheses", np.uint32), ("threshold", np.float32), ("min_gap", np.float32),
+    ("refine_iters", np.uint32), ("min_inliers", np.uint32), ("seed_lo", np.uint32), ("seed_hi", np.uint32), ("set_id_base", np.uint32),
+    ("outputs", np.uint32), ("_pad", np.uint32, (5,)),
+])
+assert POSE_ALIGN_PARAMS_DTYPE.itemsize == 64
+
+
+class PoseAlignOut(C.Structure):
+    """slhip_pose_align_out: the output pointers of slhip_pose_align."""
+
+    _fields_ = [("pose", C.c_void_p), ("n_inliers", C.c_void_p), ("rms", C.c_void_p), ("inliers", C.c_void_p), ("best", C.c_void_p),
+                ("flags", C.c_void_p)]
+
+
 # slhip_pose_icp_params (include/slhip.h), 64 bytes
 POSE_ICP_PARAMS_DTYPE = np.dtype([
     ("n_sets", np.uint32), ("n_points", np.uint32), ("max_iters", np.uint32), ("min_pairs", np.uint32), ("max_dist", np.float32),
@@ -499,6 +518,7 @@ SYNTH_STREAM_CROP = 5    # Philox stream of the crop jitter (slhip_object_crops_
 SYNTH_STREAM_POINTS = 6  # Philox stream of the point ranks (slhip_object_points_gather)
 SYNTH_STREAM_PNP = 7     # Philox stream of the correspondence samples (slhip_pose_pnp)
 SYNTH_STREAM_VOTE = 8    # Philox stream of the voter samples (slhip_keypoint_vote)
+SYNTH_STREAM_ALIGN = 9   # Philox stream of the alignment samples (slhip_pose_align)
 SYNTH_SAMPLE_DISTINCT = 1
 SYNTH_RANDOM_PBR = 2
 SYNTH_SHADOWS = 4
@@ -693,6 +713,12 @@ def lib():
         L.slhip_pose_fit_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseFitOut)]
         L.slhip_pose_fit_timing_enable.argtypes = [C.c_int]
         L.slhip_pose_fit_timings.argtypes = [C.POINTER(C.c_float * 1)]
+    if hasattr(L, "slhip_pose_align"):               # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_pose_align_check_params.argtypes = [C.c_void_p]
+        L.slhip_pose_align.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseAlignOut), C.c_void_p]
+        L.slhip_pose_align_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseAlignOut)]
+        L.slhip_pose_align_timing_enable.argtypes = [C.c_int]
+        L.slhip_pose_align_timings.argtypes = [C.POINTER(C.c_float * 1)]
     if hasattr(L, "slhip_pose_icp"):                 # (absent from older builds selected through SLHIP_LIB for A/B runs)
         L.slhip_pose_icp_check_params.argtypes = [C.c_void_p]
         L.slhip_pose_icp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseBank), C.POINTER(PoseIcpOut), C.c_void_p]

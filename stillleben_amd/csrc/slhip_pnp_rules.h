@@ -23,6 +23,7 @@
 
 #include "slhip.h"
 #include "slhip_pose_rules.h"      // row_point, is_finite, pixel_u, BLOCK, WAVE, block_sum
+#include "slhip_ransac_rules.h"    // pick, key_of, key_count, key_best
 #include "slhip_rng.h"             // Philox
 
 namespace slhip_pnp {
@@ -30,6 +31,9 @@ namespace slhip_pnp {
 using slhip_pose::is_finite;
 using slhip_pose::pixel_u;
 using slhip_pose::row_point;
+using slhip_ransac::key_best;
+using slhip_ransac::key_count;
+using slhip_ransac::key_of;
 
 constexpr uint32_t BLOCK = slhip_pose::BLOCK;
 constexpr uint32_t WAVE = slhip_pose::WAVE;
@@ -38,7 +42,6 @@ constexpr int BISECT = 24;                    // halvings per root of the cascad
 constexpr int POLISH = 3;                     // Newton steps on the three distances per solution
 constexpr float SIDE_TOL = 1.0f / 1024.0f;    // a polished solution may miss a squared side by this share of it
 constexpr int SUMS = 27;                      // 21 of J^T J (upper triangle, rows upwards), 6 of J^T r
-constexpr int SLOT_BITS = 13;                 // arg-max key: (count << 13) | (4097 - slot), slot = h + 1 (0: the caller's pose)
 
 struct Camera {
     float fx, fy, cx, cy;
@@ -50,8 +53,6 @@ SLHIP_HD bool valid(float u, float v, float x, float y, float z, float w)
     return is_finite(u) && is_finite(v) && is_finite(x) && is_finite(y) && is_finite(z) && w > 0.0f;
 }
 
-SLHIP_HD float uniform(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
 // rule 2: the four picks of hypothesis h among n_valid; false when two of them coincide (the hypothesis is void)
 SLHIP_HD bool sample(uint32_t key0, uint32_t key1, uint32_t set_id, uint32_t h, uint32_t n_valid, uint32_t* idx)
 {
@@ -60,10 +61,7 @@ SLHIP_HD bool sample(uint32_t key0, uint32_t key1, uint32_t set_id, uint32_t h, 
     p.k[0] = key0; p.k[1] = key1;
     p.block();
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t i = (uint32_t)(uniform(p.c[k]) * (float)n_valid);
-        idx[k] = i < n_valid - 1u ? i : n_valid - 1u;
-    }
+    for (int k = 0; k < 4; ++k) idx[k] = slhip_ransac::pick(p.c[k], n_valid);
     return idx[0] != idx[1] && idx[0] != idx[2] && idx[0] != idx[3] && idx[1] != idx[2] && idx[1] != idx[3] && idx[2] != idx[3];
 }
 
@@ -283,10 +281,6 @@ SLHIP_HD bool hypothesis(uint32_t key0, uint32_t key1, uint32_t set_id, uint32_t
     }
     return have;
 }
-
-SLHIP_HD uint32_t key_of(uint32_t count, uint32_t slot) { return (count << SLOT_BITS) | (4097u - slot); }
-SLHIP_HD uint32_t key_count(uint32_t key) { return key >> SLOT_BITS; }
-SLHIP_HD int key_best(uint32_t key) { return (int)(4097u - (key & ((1u << SLOT_BITS) - 1u))) - 1; }
 
 // ---- rule 5: the refinement -----------------------------------------------------------------------------------------------------
 // the 27 terms of an inlier: acc[..] = acc[..] + term

@@ -639,10 +639,32 @@ class SceneBatch:
             raise TypeError("SceneBatch.pose_fit takes either (src, dst) tensors or a KeypointVotes3D with `bank=`")
         return pose_fit.solve(src, dst, **kw)
 
+    def pose_align(self, src, dst=None, bank=None, coord=None, **kw):
+        """sl.pose_align.solve with the Philox key of the view last placed and the first scene id of the batch as the set id
+        base: a PoseAlign with one pose (object to camera) per set, the one with the most inliers, refitted on them.  Either an
+        ObjectPoints with its `coord` and `camera` outputs (`coord=`: float32 [n, K, 4] coordinates that replace the rendered
+        ones, a network's prediction), or a KeypointVotes3D with `bank=` (a KeypointBank or a float32 [A, Kp, 4] tensor: the
+        bank's keypoints of every set's class onto the voted ones), or a pair of float32 [n, K, 4] tensors.  `kw`: threshold
+        (required, in the unit of the points), n_hypotheses, refine_iters, min_gap, min_inliers, outputs, init.
+        pose_align(...).dense(B, O, points.scene_global, points.slot) is the [B, O, 3, 4] that pose_errors and pose_vsd take."""
+        from . import keypoint_vote3d, pose_align
+
+        for name in ("seed", "set_id_base"):
+            if name in kw:
+                raise TypeError("SceneBatch.pose_align sets `%s` itself" % name)
+        if isinstance(src, keypoint_vote3d.KeypointVotes3D):
+            if dst is not None or bank is None or coord is not None:
+                raise TypeError("SceneBatch.pose_align takes a KeypointVotes3D with `bank=` and without `dst` and `coord`")
+            src, dst = src.correspondences(bank)
+        elif bank is not None:
+            raise TypeError("SceneBatch.pose_align takes an ObjectPoints, (src, dst) tensors or a KeypointVotes3D with `bank=`")
+        key = _abi.view_key(int(self.params["seed_lo"]), int(self.params["seed_hi"]), self.view)
+        return pose_align.solve(src, dst, coord=coord, seed=key, set_id_base=int(self.params["scene_id_base"]), **kw)
+
     def pose_icp(self, points, init, bank, **kw):
         """sl.pose_icp.solve on the point sets of a render (`points` = what points(...) returned, with its `camera` output): a
-        PoseICP with one refined pose (object to camera) per set.  `init`: the initial poses as float32 [n, 3, 4], a PoseFit or
-        PosePnP (its `.pose`), or float32 [B, O, 3, 4] for all scenes of the batch, gathered by points.scene_global and
+        PoseICP with one refined pose (object to camera) per set.  `init`: the initial poses as float32 [n, 3, 4], a PoseFit,
+        PoseAlign or PosePnP (its `.pose`), or float32 [B, O, 3, 4] for all scenes of the batch, gathered by points.scene_global and
         points.slot.  `bank`: a ModelBank of the batch's table (sl.pose_error.bank(table, ...); surface-sampled points from
         sl.pose_icp.surface_points serve low-poly classes).  The class of every set's object comes from the batch's object
         records.  `kw`: max_iters, max_dist, dist_scale, min_dist, min_pairs, min_gap, tol_rot, tol_trans, outputs.
@@ -658,7 +680,7 @@ class SceneBatch:
         if not isinstance(init, torch.Tensor):
             init = getattr(init, "pose", None)
             if init is None:
-                raise TypeError("SceneBatch.pose_icp: `init` must be a tensor, or a PoseFit / PosePnP with its `pose` output")
+                raise TypeError("SceneBatch.pose_icp: `init` must be a tensor, or a PoseFit / PoseAlign / PosePnP with its `pose` output")
         scene, slot = points.scene_global.long(), (points.slot - 1).long()
         if init.dim() == 4:
             if not init.is_cuda:

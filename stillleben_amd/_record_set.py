@@ -1,7 +1,8 @@
 """What sl.object_crops and sl.object_points share: the record-set class behind ObjectCrops and ObjectPoints and the select step
 of their extract() -- statistics (and mask records) to a compact array of records in ascending (scene, slot) order.  And what the
-pose family shares (pose_fit, pose_icp, pose_pnp, keypoint_vote, keypoint_vote3d): OutputSet, the class behind their results,
-which derives the outputs' names, arrays and ctypes record from one table per module."""
+pose family shares (pose_fit, pose_icp, pose_pnp, pose_align, keypoint_vote, keypoint_vote3d): OutputSet, the class behind their
+results, which derives the outputs' names, arrays and ctypes record from one table per module, and set_key, the seed of a
+parameter record."""
 import ctypes as C
 
 import numpy as np
@@ -63,10 +64,11 @@ def output_bits(outputs, known):
     return bits
 
 
-def set_key(p, seed, scene_id_base):
-    """seed_lo, seed_hi and scene_id_base of a params record.  `seed`: an integer, or the (lo, hi) pair of a Philox key."""
+def set_key(p, seed, id_base, base_field="scene_id_base"):
+    """seed_lo, seed_hi and the id base (`base_field`) of a params record.  `seed`: an integer, or the (lo, hi) pair of a Philox
+    key."""
     lo, hi = seed if isinstance(seed, (tuple, list)) else (int(seed), int(seed) >> 32)
-    p["seed_lo"], p["seed_hi"], p["scene_id_base"] = int(lo) & 0xFFFFFFFF, int(hi) & 0xFFFFFFFF, int(scene_id_base) & 0xFFFFFFFF
+    p["seed_lo"], p["seed_hi"], p[base_field] = int(lo) & 0xFFFFFFFF, int(hi) & 0xFFFFFFFF, int(id_base) & 0xFFFFFFFF
 
 
 def rendered(name, buffers, need):
@@ -192,3 +194,17 @@ class PoseSet(OutputSet):
         out = torch.full((int(B), int(O), 3, 4), float("nan"), dtype=torch.float32, device=self.pose.device)
         out[torch.as_tensor(scene, device=out.device).long(), torch.as_tensor(slot, device=out.device).long() - 1] = self.pose
         return out
+
+
+class InlierPoseSet(PoseSet):
+    """A PoseSet of sets of K correspondences with inlier bits (pose_pnp, pose_align); `n_points`: K."""
+
+    def __init__(self, n_points, pose=None, n_inliers=None, rms=None, inliers=None, best=None, flags=None):
+        super().__init__(pose=pose, n_inliers=n_inliers, rms=rms, inliers=inliers, best=best, flags=flags)
+        self.n_points = int(n_points)
+
+    def inlier_mask(self):
+        """bool [M, K]: correspondence j of a set is an inlier of its pose"""
+        if self.inliers is None:
+            raise RuntimeError("%s: the `inliers` output was not asked for" % self.NAME)
+        return bit_mask(self.inliers, self.n_points)

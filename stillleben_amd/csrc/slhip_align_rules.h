@@ -24,6 +24,7 @@ using slhip_fit::is_finite;
 using slhip_ransac::key_best;
 using slhip_ransac::key_count;
 using slhip_ransac::key_of;
+using slhip_ransac::pose_finite;
 
 constexpr uint32_t BLOCK = slhip_fit::BLOCK;
 constexpr uint32_t WAVE = slhip_fit::WAVE;
@@ -40,14 +41,6 @@ SLHIP_HD bool sample(uint32_t key0, uint32_t key1, uint32_t set_id, uint32_t h, 
     idx[1] = slhip_ransac::pick(p.c[1], n_valid);
     idx[2] = slhip_ransac::pick(p.c[2], n_valid);
     return idx[0] != idx[1] && idx[0] != idx[2] && idx[1] != idx[2];
-}
-
-SLHIP_HD bool pose_finite(const float* M)
-{
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ok = ok && is_finite(M[i]);
-    return ok;
 }
 
 // rule 3: the fit's rules 2 to 6 on the three pairs (s[k], d[k]), every sum ((p0 + p1) + p2) from the first term on.  False when

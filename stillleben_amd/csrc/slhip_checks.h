@@ -60,13 +60,15 @@ inline int check_min_gap(const char* who, float min_gap)
 
 // One optional output of a module's output record: the bit of `outputs` that names it and its pointer.  The two checks below take
 // the whole record as a brace list: const slhip::OutputList outputs = {{SLHIP_X_OUT_A, out->a}, {SLHIP_X_OUT_B, out->b}, ...};
+// (or as any other range of NamedOutput, such as a std::array that a function returns)
 struct NamedOutput {
     uint32_t bit;
     const void* ptr;
 };
 using OutputList = std::initializer_list<NamedOutput>;
 
-inline int check_outputs_present(const char* who, uint32_t outputs, OutputList all)
+template <class List>
+int check_outputs_present(const char* who, uint32_t outputs, const List& all)
 {
     for (const NamedOutput& o : all)
         if ((outputs & o.bit) && !o.ptr) {
@@ -76,7 +78,8 @@ inline int check_outputs_present(const char* who, uint32_t outputs, OutputList a
     return 0;
 }
 
-inline int check_outputs_aligned(const char* who, uint32_t outputs, OutputList all)
+template <class List>
+int check_outputs_aligned(const char* who, uint32_t outputs, const List& all)
 {
     for (const NamedOutput& o : all)
         if ((outputs & o.bit) && ((uintptr_t)o.ptr & 3u)) {

@@ -34,6 +34,7 @@ using slhip_pose::row_point;
 using slhip_ransac::key_best;
 using slhip_ransac::key_count;
 using slhip_ransac::key_of;
+using slhip_ransac::pose_finite;
 
 constexpr uint32_t BLOCK = slhip_pose::BLOCK;
 constexpr uint32_t WAVE = slhip_pose::WAVE;
@@ -358,14 +359,6 @@ SLHIP_HD bool step(const float* S, float* M)
 #pragma unroll
     for (int i = 0; i < 12; ++i) M[i] = N[i];
     return true;
-}
-
-SLHIP_HD bool pose_finite(const float* M)
-{
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) ok = ok && is_finite(M[i]);
-    return ok;
 }
 
 }  // namespace slhip_pnp

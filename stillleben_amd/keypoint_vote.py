@@ -41,8 +41,7 @@ def make_params(size, n_sets, n_points, n_keypoints, n_hypotheses=128, inlier_co
     p["W"], p["H"] = int(size[0]), int(size[1])
     p["n_sets"], p["n_points"], p["n_keypoints"], p["n_hypotheses"] = int(n_sets), int(n_points), int(n_keypoints), int(n_hypotheses)
     p["inlier_cos"], p["min_inliers"], p["min_sin"] = np.float32(inlier_cos), int(min_inliers), np.float32(min_sin)
-    lo, hi = seed if isinstance(seed, (tuple, list)) else (int(seed), int(seed) >> 32)
-    p["seed_lo"], p["seed_hi"], p["set_id_base"] = int(lo) & 0xFFFFFFFF, int(hi) & 0xFFFFFFFF, int(set_id_base) & 0xFFFFFFFF
+    _record_set.set_key(p, seed, set_id_base, "set_id_base")
     p["outputs"] = outputs if isinstance(outputs, int) else _record_set.output_bits(outputs, OUTPUTS)
     return p
 

@@ -28,7 +28,7 @@ FLAGS = {"insufficient": _abi.ALIGN_INSUFFICIENT, "no_model": _abi.ALIGN_NO_MODE
 n_words = _record_set.n_words
 
 
-class PoseAlign(_record_set.PoseSet):
+class PoseAlign(_record_set.InlierPoseSet):
     """The pose of every set (torch tensors on the device from `solve`, numpy arrays from `solve_host`; those not asked for
     are None):
         pose       float32 [M, 3, 4] object to camera       n_inliers  int32 [M]
@@ -43,16 +43,6 @@ class PoseAlign(_record_set.PoseSet):
     TABLE = (("pose", _abi.ALIGN_OUT_POSE, (3, 4), np.float32), ("n_inliers", _abi.ALIGN_OUT_N_INLIERS, (), np.int32),
              ("rms", _abi.ALIGN_OUT_RMS, (), np.float32), ("inliers", _abi.ALIGN_OUT_INLIERS, ("words",), np.uint32),
              ("best", _abi.ALIGN_OUT_BEST, (), np.int32), ("flags", _abi.ALIGN_OUT_FLAGS, (), np.int32))
-
-    def __init__(self, n_points, pose=None, n_inliers=None, rms=None, inliers=None, best=None, flags=None):
-        super().__init__(pose=pose, n_inliers=n_inliers, rms=rms, inliers=inliers, best=best, flags=flags)
-        self.n_points = int(n_points)
-
-    def inlier_mask(self):
-        """bool [M, K]: correspondence j of a set is an inlier of its pose"""
-        if self.inliers is None:
-            raise RuntimeError("pose_align: the `inliers` output was not asked for")
-        return _record_set.bit_mask(self.inliers, self.n_points)
 
 
 OUTPUTS = PoseAlign.OUTPUTS
@@ -69,8 +59,7 @@ def make_params(n_sets, n_points, threshold, n_hypotheses=256, refine_iters=4, m
     p["n_sets"], p["n_points"], p["n_hypotheses"] = int(n_sets), int(n_points), int(n_hypotheses)
     p["threshold"], p["min_gap"] = np.float32(threshold), np.float32(min_gap)
     p["refine_iters"], p["min_inliers"] = int(refine_iters), int(min_inliers)
-    lo, hi = seed if isinstance(seed, (tuple, list)) else (int(seed), int(seed) >> 32)
-    p["seed_lo"], p["seed_hi"], p["set_id_base"] = int(lo) & 0xFFFFFFFF, int(hi) & 0xFFFFFFFF, int(set_id_base) & 0xFFFFFFFF
+    _record_set.set_key(p, seed, set_id_base, "set_id_base")
     p["outputs"] = outputs if isinstance(outputs, int) else _record_set.output_bits(outputs, OUTPUTS)
     return p
 

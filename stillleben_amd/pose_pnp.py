@@ -25,7 +25,7 @@ FLAGS = {"insufficient": _abi.PNP_INSUFFICIENT, "no_model": _abi.PNP_NO_MODEL, "
 n_words = _record_set.n_words
 
 
-class PosePnP(_record_set.PoseSet):
+class PosePnP(_record_set.InlierPoseSet):
     """The pose of every set (torch tensors on the device from `solve`, numpy arrays from `solve_host`; those not asked for
     are None):
         pose       float32 [M, 3, 4] object to camera       n_inliers  int32 [M]
@@ -40,16 +40,6 @@ class PosePnP(_record_set.PoseSet):
              ("rms", _abi.PNP_OUT_RMS, (), np.float32), ("inliers", _abi.PNP_OUT_INLIERS, ("words",), np.uint32),
              ("best", _abi.PNP_OUT_BEST, (), np.int32), ("flags", _abi.PNP_OUT_FLAGS, (), np.int32))
 
-    def __init__(self, n_points, pose=None, n_inliers=None, rms=None, inliers=None, best=None, flags=None):
-        super().__init__(pose=pose, n_inliers=n_inliers, rms=rms, inliers=inliers, best=best, flags=flags)
-        self.n_points = int(n_points)
-
-    def inlier_mask(self):
-        """bool [M, K]: correspondence j of a set is an inlier of its pose"""
-        if self.inliers is None:
-            raise RuntimeError("pose_pnp: the `inliers` output was not asked for")
-        return _record_set.bit_mask(self.inliers, self.n_points)
-
 
 OUTPUTS = PosePnP.OUTPUTS
 _ALL = tuple(OUTPUTS)
@@ -63,8 +53,7 @@ def make_params(intrinsics, n_sets, n_points, n_hypotheses=256, threshold_px=2.0
     p["fx"], p["fy"], p["cx"], p["cy"] = (np.float32(v) for v in intrinsics)
     p["n_sets"], p["n_points"], p["n_hypotheses"] = int(n_sets), int(n_points), int(n_hypotheses)
     p["threshold_px"], p["refine_iters"], p["min_inliers"] = np.float32(threshold_px), int(refine_iters), int(min_inliers)
-    lo, hi = seed if isinstance(seed, (tuple, list)) else (int(seed), int(seed) >> 32)
-    p["seed_lo"], p["seed_hi"], p["set_id_base"] = int(lo) & 0xFFFFFFFF, int(hi) & 0xFFFFFFFF, int(set_id_base) & 0xFFFFFFFF
+    _record_set.set_key(p, seed, set_id_base, "set_id_base")
     p["outputs"] = outputs if isinstance(outputs, int) else _record_set.output_bits(outputs, OUTPUTS)
     return p
 

@@ -285,12 +285,12 @@ def host_call(null=None, misalign=None, Hy=8, init=True, mask=63):
     uv, xyz, k4, t0 = np.zeros((M * K * 2 + 4), F), np.zeros((M * K * 4 + 4), F), np.zeros(M * 4 + 4, F), np.zeros(M * 12 + 4, F)
     outs = {k: np.full(64, 0x5A5A5A5A, np.uint32) for k in NAMES}
     ptr = {"uv": uv.ctypes.data, "xyz": xyz.ctypes.data, "intrinsics": k4.ctypes.data, "init": t0.ctypes.data if init else None}
-    if misalign:
+    if misalign in ptr:
         ptr[misalign] += 4
     for k in ("uv", "xyz"):
         if null == k:
             ptr[k] = None
-    o = _abi.PosePnpOut(*(None if null == k else outs[k].ctypes.data for k in NAMES))
+    o = _abi.PosePnpOut(*(None if null == k else outs[k].ctypes.data + (2 if misalign == k else 0) for k in NAMES))
     p = pnp.make_params(K4, M, K, n_hypotheses=Hy, outputs=mask).reshape(1)
     st = _abi.lib().slhip_pose_pnp_host(None if null == "params" else p.ctypes.data, ptr["uv"], ptr["xyz"], ptr["intrinsics"], ptr["init"],
                                         None if null == "record" else C.byref(o))
@@ -299,10 +299,12 @@ def host_call(null=None, misalign=None, Hy=8, init=True, mask=63):
 
 @pytest.mark.parametrize("kw", [dict(null="params"), dict(null="uv"), dict(null="xyz"), dict(null="record"), dict(null="pose"),
                                 dict(null="inliers"), dict(null="flags"), dict(misalign="uv"), dict(misalign="xyz"),
-                                dict(misalign="intrinsics"), dict(Hy=0, init=False)])
+                                dict(misalign="intrinsics"), dict(misalign="rms"), dict(Hy=0, init=False)])
 def test_entries_refuse_bad_arguments(kw):
     st, outs = host_call(**kw)
     assert st < 0 and _abi.lib().slhip_last_error()
+    if kw == dict(misalign="rms"):
+        assert "4-byte aligned" in _abi.lib().slhip_last_error().decode()
     for k in NAMES:
         assert (outs[k] == 0x5A5A5A5A).all(), k
     assert host_call()[0] == 0

@@ -25,7 +25,7 @@ import _step_timing  # noqa: E402
 REP = max(3, int(sys.argv[1]) if len(sys.argv) > 1 else 10)
 M = int(sys.argv[2]) if len(sys.argv) > 2 else 2048
 K4 = (572.4, 572.4, 320.0, 240.0)
-SCORE_VALU = 43                            # VALU instructions of one point test: 343 per 8 tests in the main score loop (DESIGN.md "Pose PnP")
+SCORE_VALU = 53                            # VALU instructions of one point test: 213 per 4 tests in the main score loop (DESIGN.md "Pose PnP")
 LANE_RATE = 256 * 4 * 16 * 2.4e9           # lane-instructions per second of the device
 sl.init_cuda(0)
 dev = torch.device("cuda", 0)

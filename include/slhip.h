@@ -53,7 +53,8 @@ extern "C" {
                                     slhip_object_regions_check_params, _centres_bytes, _centres, _centres_host, _vertices,
                                     _vertices_host, _label, _label_host, _timing_enable, _timings;
                                     slhip_pose_error_check_params, _diameter, _diameter_host, slhip_pose_error,
-                                    slhip_pose_error_host, _timing_enable, _timings */
+                                    slhip_pose_error_host, _timing_enable, _timings;
+                                    slhip_render_flow_check_params, slhip_render_flow, _host, _motion, _motion_host */
 #define SLHIP_NUM_LIGHTS 3 /* reference include/stillleben/common.h:17 */
 
 /* ---------------------------------------------------------------------------------------------
@@ -1786,6 +1787,89 @@ int slhip_pose_icp_host(const slhip_pose_icp_params* params, const float* h_came
 /* Developer hook (tools/time_pose_icp.py): HIP events round the last slhip_pose_icp [0] (-1: not run). */
 int slhip_pose_icp_timing_enable(int on);
 int slhip_pose_icp_timings(float ms_out[1]);
+
+/* ---------------------------------------------------------------------------------------------
+ * Render flow: where every pixel of one render (picture a) lands in another render of the same scene
+ * (picture b) -- optical flow, scene flow and an occlusion flag, the targets of flow networks (RAFT)
+ * and of flow-based 6D refiners (Coupled Iterative Refinement, SCFlow, PFA, GenFlow, DeepIM's flow
+ * head), and the co-visibility of a view pair.  Stands in for nothing on the reference's side: this
+ * project's addition, the reference has no counterpart.  Exact geometry and exact motion: the depth of
+ * a (the w of its coord target), its instance plane and, per instance slot, the rigid motion from
+ * camera frame a to camera frame b.  Both pictures share the intrinsics and the size.  All float32,
+ * one rounded IEEE operation at a time (no fma), the parenthesisation below is the contract;
+ * csrc/slhip_flow_rules.h holds the rules for host and device (with row_point, project, is_finite and
+ * unoccluded of "Object keypoints"), tests/render_flow_ref.py restates them in NumPy bit for bit.
+ * DESIGN.md "Render flow".
+ *
+ * Motion table: f32 [B, n_slots, 3, 4], row-major; row i maps a point of camera frame a to camera
+ * frame b for the pixels of instance i.  Slot 0 is the plane and the background: the camera's own motion.
+ *
+ * Pixel (x, y) of scene b of picture a, with z = its depth, i = its instance (read as u16), M = row i:
+ *   VALID   z finite and 0 < z < max_depth;  i < n_slots;  all 12 entries of M finite;  the moved point in
+ *           front (X', Y', Z' finite and Z' > 0).  The renderer writes 3000 where nothing was hit, so
+ *           max_depth = 3000 drops the background and keeps the plane.
+ *   X = (((x + 0.5f) - cx) * z) / fx;   Y = (((y + 0.5f) - cy) * z) / fy             (the camera point of "Object points")
+ *   X' = ((M[0] * X + M[1] * Y) + M[2] * z) + M[3], Y' and Z' by rows 1 and 2;
+ *   u = (fx * X') / Z' + cx;   v = (fy * Y') / Z' + cy
+ *   INSIDE  VALID, 0 <= u < W and 0 <= v < H
+ *   flow = (u - (x + 0.5f), v - (y + 0.5f));   scene_flow = (X' - X, Y' - Y, Z' - z)
+ *   VISIBLE only with a depth plane of picture b:  x0 = floor(u - 0.5f), y0 = floor(v - 0.5f); of the
+ *           pixels (x0 + dx, y0 + dy), dx, dy in {0, 1} -- the bilinear footprint of (u, v), tried in the order
+ *           (0,0), (1,0), (0,1), (1,1) -- those inside the picture; one passes when (with
+ *           SLHIP_FLOW_MATCH_INSTANCE and an instance plane of b) its instance in b equals i, and its depth z_b
+ *           is finite, z_b > 0 and Z' <= z_b + (depth_tol + depth_rel * Z').  VISIBLE = VALID, INSIDE and any passes.
+ * A pixel that is not VALID gets zeros and flags 0: the flags plane is the mask.
+ * counts[b][i] = (pixels of a with instance i, of those the VALID, the INSIDE, the VISIBLE ones): integer
+ * sums, the same in any order.
+ *
+ * Motion of one rigid frame, slhip_render_flow_motion: out = to o inv_rigid(from) on rows 0-2 of two
+ * row-major 3 x 4 matrices (R, t):  inv_rigid = (R^T, -(R^T t)), every dot product summed as
+ * (a*b + c*d) + e*f, the product's rotation entries the same way, its translation by the row rule of X'
+ * above.  A non-finite entry among the 24 gives 12 NaNs (so those pixels are not VALID).  Rigid inputs are
+ * assumed and not checked.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_FLOW_SLOTS_MAX 256
+#define SLHIP_FLOW_VALID   1u
+#define SLHIP_FLOW_INSIDE  2u
+#define SLHIP_FLOW_VISIBLE 4u
+#define SLHIP_FLOW_OUT_FLOW   1u
+#define SLHIP_FLOW_OUT_SCENE  2u
+#define SLHIP_FLOW_OUT_FLAGS  4u
+#define SLHIP_FLOW_OUT_COUNTS 8u
+#define SLHIP_FLOW_MATCH_INSTANCE 1u
+
+typedef struct {
+    float fx, fy, cx, cy;      /* intrinsics of both pictures: fx, fy > 0, all four finite                    */
+    int32_t W, H;              /* size of both pictures, each side 1..32768                                   */
+    uint32_t n_slots;          /* rows of a scene's motion table, 1..SLHIP_FLOW_SLOTS_MAX                     */
+    float max_depth;           /* > 0, may be +inf: a pixel of a at or beyond it is not VALID                 */
+    float depth_tol;           /* finite and >= 0: how far behind b's surface a moved point still shows       */
+    float depth_rel;           /* finite and >= 0: the same as a share of Z'                                  */
+    uint32_t outputs;          /* SLHIP_FLOW_OUT_* bits, at least one                                         */
+    uint32_t flags;            /* SLHIP_FLOW_MATCH_INSTANCE                                                   */
+} slhip_render_flow_params; /* 48 bytes */
+
+/* Every rule of the record, in the order of its fields.  A negative error with slhip_last_error text.  No device. */
+int slhip_render_flow_check_params(const slhip_render_flow_params* params);
+/* d_depth_a / stride_a: the depth of picture a, read at pixel * stride (1: a float plane [B, H, W]; 4: d_coord + 3, the w
+ * of the coord target in place), d_depth_b / stride_b the same of picture b or NULL: VISIBLE is then never set and its count
+ * is 0.  d_instance_a u16 [B, H, W]; d_instance_b the same or NULL: no instance condition.  d_motion f32 [B, n_slots, 3, 4].
+ * Outputs, each only with its SLHIP_FLOW_OUT_* bit (without it the pointer is not read): d_flow f32 [B, H, W, 2] (8-byte
+ * aligned), d_scene_flow f32 [B, H, W, 3], d_flags u8 [B, H, W], d_counts i32 [B, n_slots, 4], zeroed by the call itself on
+ * `stream`.  B == 0 does nothing; B > 65535, null pointers, a zero stride, misalignment and bad parameters are refused before
+ * anything touches the device.  One lane per pixel, the scene's motion table in LDS.  Asynchronous on `stream`.             */
+int slhip_render_flow(const slhip_render_flow_params* params, const float* d_depth_a, uint32_t stride_a,
+                      const uint16_t* d_instance_a, const float* d_motion, const float* d_depth_b, uint32_t stride_b,
+                      const uint16_t* d_instance_b, uint32_t B, float* d_flow, float* d_scene_flow, uint8_t* d_flags,
+                      int32_t* d_counts, void* stream);
+/* d_from, d_to, d_out: f32 [n, 3, 4]; one lane per frame.  n == 0 does nothing.  Asynchronous on `stream`. */
+int slhip_render_flow_motion(const float* d_from, const float* d_to, uint32_t n, float* d_out, void* stream);
+/* The same rules on host arrays through csrc/slhip_flow_rules.h.  Host only, no device: the handles the CPU tests use. */
+int slhip_render_flow_host(const slhip_render_flow_params* params, const float* h_depth_a, uint32_t stride_a,
+                           const uint16_t* h_instance_a, const float* h_motion, const float* h_depth_b, uint32_t stride_b,
+                           const uint16_t* h_instance_b, uint32_t B, float* h_flow, float* h_scene_flow, uint8_t* h_flags,
+                           int32_t* h_counts);
+int slhip_render_flow_motion_host(const float* h_from, const float* h_to, uint32_t n, float* h_out);
 
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle

@@ -19,6 +19,7 @@ from stillleben_amd import keypoint_vote3d, KeypointVotes3D  # noqa: F401  (addi
 from stillleben_amd import pose_fit, PoseFit  # noqa: F401  (additive: the pose of every set of 3D-3D correspondences)
 from stillleben_amd import pose_align, PoseAlign  # noqa: F401  (additive: the robust pose of every set of 3D-3D correspondences)
 from stillleben_amd import pose_icp, PoseICP  # noqa: F401  (additive: ICP refinement of a pose against the depth's camera points)
+from stillleben_amd import render_flow, RenderFlow  # noqa: F401  (additive: optical flow, scene flow and occlusion between two renders)
 
 __all__ = _impl.__all__
 for _name in ("camera_model", "diff", "extension", "losses", "profiling"):

@@ -50,6 +50,8 @@ from . import pose_align  # noqa: F401  (additive: the pose of every set of 3D-3
 from .pose_align import PoseAlign  # noqa: F401
 from . import pose_icp  # noqa: F401  (additive: ICP refinement of a pose against the depth's camera points, on a model bank)
 from .pose_icp import PoseICP  # noqa: F401
+from . import render_flow  # noqa: F401  (additive: optical flow, scene flow and occlusion between two renders of a scene)
+from .render_flow import RenderFlow  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -66,6 +68,7 @@ __all__ = [
     'pose_fit', 'PoseFit',
     'pose_align', 'PoseAlign',
     'pose_icp', 'PoseICP',
+    'render_flow', 'RenderFlow',
 ]
 
 

@@ -77,6 +77,10 @@ ICP_BAD_CLASS, ICP_NO_INIT, ICP_INSUFFICIENT, ICP_DEGENERATE, ICP_CONVERGED = 1,
 ICP_FAILED = 15                                                                  # SLHIP_ICP_FAILED: the failure bits
 REGIONS_MAX, REGION_NONE = 255, 255                                   # SLHIP_REGIONS_MAX, SLHIP_REGION_NONE
 REGIONS_OUT_LOCAL, REGIONS_OUT_HISTOGRAM = 1, 2                        # SLHIP_REGIONS_OUT_*
+FLOW_SLOTS_MAX = 256                                                   # SLHIP_FLOW_SLOTS_MAX
+FLOW_VALID, FLOW_INSIDE, FLOW_VISIBLE = 1, 2, 4                        # SLHIP_FLOW_*: the flag bits of a pixel of the render flow
+FLOW_OUT_FLOW, FLOW_OUT_SCENE, FLOW_OUT_FLAGS, FLOW_OUT_COUNTS = 1, 2, 4, 8      # SLHIP_FLOW_OUT_*
+FLOW_MATCH_INSTANCE = 1                                                # SLHIP_FLOW_MATCH_INSTANCE (params.flags)
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
 COMM_ID_BYTES = 128
@@ -304,6 +308,13 @@ OBJECT_REGION_PARAMS_DTYPE = np.dtype([
     ("n_assets", np.uint32), ("outputs", np.uint32), ("_pad", np.uint32),
 ])
 assert OBJECT_REGION_PARAMS_DTYPE.itemsize == 32
+# slhip_render_flow_params (include/slhip.h), 48 bytes
+RENDER_FLOW_PARAMS_DTYPE = np.dtype([
+    ("fx", np.float32), ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("W", np.int32), ("H", np.int32),
+    ("n_slots", np.uint32), ("max_depth", np.float32), ("depth_tol", np.float32), ("depth_rel", np.float32), ("outputs", np.uint32),
+    ("flags", np.uint32),
+])
+assert RENDER_FLOW_PARAMS_DTYPE.itemsize == 48
 # slhip_pose_error_params (include/slhip.h), 32 bytes
 POSE_ERROR_PARAMS_DTYPE = np.dtype([
     ("fx", np.float32), ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("n_objects", np.uint32),
@@ -725,6 +736,13 @@ def lib():
         L.slhip_pose_icp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PoseBank), C.POINTER(PoseIcpOut)]
         L.slhip_pose_icp_timing_enable.argtypes = [C.c_int]
         L.slhip_pose_icp_timings.argtypes = [C.POINTER(C.c_float * 1)]
+    if hasattr(L, "slhip_render_flow"):              # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_render_flow_check_params.argtypes = [C.c_void_p]
+        L.slhip_render_flow.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slhip_render_flow_host.argtypes = L.slhip_render_flow.argtypes[:-1]
+        L.slhip_render_flow_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.slhip_render_flow_motion_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

@@ -521,6 +521,48 @@ class SceneBatch:
         return object_regions.label(buffers.instance[:B], buffers.coord[:B], self.d_objects[s0 * nb:(s0 + B) * nb], bank,
                                     n_objects=self.n_objects, **kw)
 
+    def view_state(self):
+        """What flow() needs of the view last placed once another one is placed or the pile is settled further: an
+        sl.render_flow.ViewState with clones of `object_to_camera` [n_scenes, O, 3, 4] and of rows 0-2 of every scene's
+        world_to_cam [n_scenes, 3, 4], read from the scene records on the device (no host round trip).  Needs
+        place(object_to_camera=True) for the view last placed.  Asynchronous on the current stream."""
+        from . import render_flow
+
+        if self.object_to_camera is None or not self._object_to_camera_placed:
+            raise RuntimeError("SceneBatch.view_state needs object_to_camera of the view last placed: call "
+                               "place(object_to_camera=True) (the last place() did not keep it)")
+        size, at = _abi.SCENE_DTYPE.itemsize, _abi.SCENE_DTYPE.fields["world_to_cam"][1]
+        rec = self.d_srec[:self.n_scenes * size].view(self.n_scenes, size)
+        w2c = rec[:, at:at + 48].contiguous().view(torch.float32).view(self.n_scenes, 3, 4)      # (contiguous(): the clone)
+        return render_flow.ViewState(self.object_to_camera.clone(), w2c, self.view)
+
+    def flow(self, buffers_a, state_a, buffers_b=None, state_b=None, chunk=0, **kw):
+        """sl.render_flow.compute from the render `buffers_a` of chunk `chunk` under the view `state_a` (a view_state()) to
+        the render `buffers_b` of the same chunk under `state_b` -- None: the view now placed -- with the batch's intrinsics:
+        a RenderFlow whose picture b is scene b of the chunk.  The motion table [B, O + 1, 3, 4] is built on the device:
+        slot 0 = motion(world_to_cam of a, of b), the plane and the background; slot o + 1 = motion(object_to_camera[o] of
+        a, of b).  It serves another camera on the same pile and equally the same camera after the pile was settled further
+        (place() again after settle()).  Both renders need the `coord` and `instance` targets; without `buffers_b` nothing
+        is `visible`.  `kw`: the other arguments of compute (max_depth, depth_tol, depth_rel, match_instance, outputs)."""
+        from . import render_flow
+
+        for name in ("intrinsics", "motion"):
+            if name in kw:
+                raise TypeError("SceneBatch.flow sets `%s` itself" % name)
+        if state_b is None:
+            state_b = self.view_state()
+        for buffers in (buffers_a,) + (() if buffers_b is None else (buffers_b,)):
+            if buffers.instance is None or buffers.coord is None:
+                raise RuntimeError("render_flow: the `instance` and `coord` targets were not rendered")
+        held = min(int(b.instance.shape[0]) for b in (buffers_a, buffers_b) if b is not None)
+        s0, B = self._chunk_range(chunk, held)
+        table = torch.cat([render_flow.motion(state_a.world_to_cam[s0:s0 + B], state_b.world_to_cam[s0:s0 + B])[:, None],
+                           render_flow.motion(state_a.object_to_camera[s0:s0 + B], state_b.object_to_camera[s0:s0 + B])], dim=1)
+        b_planes = (None, None) if buffers_b is None else (buffers_b.coord[:B], buffers_b.instance[:B])
+        out = render_flow.compute(buffers_a.coord[:B], buffers_a.instance[:B], table, self.intrinsics(), *b_planes, **kw)
+        out.scene0 = s0
+        return out
+
     def pose_errors(self, estimates, bank, chunk=None, **kw):
         """sl.pose_error.evaluate of pose estimates against the batch's own ground truth: its `object_to_camera`, its object
         records (read in place) and its intrinsics.  `estimates`: float32 [B, O, Hy, 3, 4] or [B, O, 3, 4] for all scenes of the

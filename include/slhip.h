@@ -1871,6 +1871,82 @@ int slhip_render_flow_host(const slhip_render_flow_params* params, const float* 
                            int32_t* h_counts);
 int slhip_render_flow_motion_host(const float* h_from, const float* h_to, uint32_t n, float* h_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Point neighbours: for every query point of a set its k nearest reference points of the same set, as
+ * lists of indices and squared distances sorted by (distance, index).  This project's addition, the
+ * reference has no counterpart: it renders, and leaves the networks' data pipeline to their loaders.
+ * What the entry replaces there is the CPU kd-tree of the FFB6D / PVN3D-with-RandLA data pipeline, per
+ * frame and encoder level (dataset's DP.knn_search, a nanoflann wrapper):
+ *   cld_nei_idx     = knn(cloud_l, cloud_l, 16)        a self-search of the first N_l points
+ *   cld_sub_idx     = the first N_l / ratio rows        no search: the reference prefix below
+ *   cld_interp_idx  = knn(cloud_l+1, cloud_l, 1)        k = 1, references = the prefix of N_l+1 points
+ *   r2p_ds_nei_idx  = knn(pixel_xyz, cloud, 16),   p2r_ds_nei_idx = knn(cloud, pixel_xyz, 1)
+ * and the k-NN grouping of PointNet++ / DGCNN style refiners on the point sets of "Object points".
+ * All float32, one rounded IEEE operation at a time (no fma), only - * + and comparisons;
+ * csrc/slhip_knn_rules.h holds the rules for host and device, so slhip_point_knn_host gives the device's
+ * outputs bit for bit, and tests/point_knn_ref.py restates them in NumPy.  DESIGN.md "Point neighbours".
+ * Per set i, query q in [0, n_queries), reference r in [0, n_refs):
+ *   1. a point (x, y, z, w) counts when w != 0 and x, y, z are finite (rule 2 of "ICP").
+ *   2. d(q, r) = dist2(query, ref) = (dx*dx + dy*dy) + dz*dz of "Pose errors", dx = query.x - ref.x.
+ *   3. r is a candidate of q when both points count, d is finite (a NaN or +inf distance is never a
+ *      neighbour), d <= max_dist * max_dist (+inf: no gate; the gate's own distance passes) and, with
+ *      skip_same, r != q -- decided by index, never by coordinates: duplicated points are normal.
+ *   4. the list of q is the first k candidates in the total order (d, r): the smaller distance first, among
+ *      equal distances the lower index; stored in that order.  As a scan upwards in r: a candidate enters
+ *      when d < the list's last distance (strictly) and goes behind every entry with d' <= d.  The order
+ *      is total, so the lists depend neither on the tiles nor on the slots of the kernel's instantiation.
+ *   5. a slot without a candidate holds idx -1 and dist2 NaN -- never 0, never a repeated neighbour;
+ *      count[q] = the filled slots, 0 for a query that does not count.
+ * A set's points lie query_stride (ref_stride) points apart in memory, stride >= count: the first n_refs
+ * points of a longer row are a reference set of their own (RandLA's sub-sample is a prefix).
+ * Bounds: n_sets * n_queries * k <= 2^31 - 1 (the elements of a list output) and
+ * n_sets * max(query_stride, ref_stride) * 4 <= 2^31 - 1 (the floats of an input); so a reference index
+ * and the 1-D grid of n_sets * ceil(n_queries / 256) workgroups fit 31 bits.  Offsets are 64-bit inside.
+ * ------------------------------------------------------------------------------------------- */
+#define SLHIP_KNN_K_MAX     32u
+#define SLHIP_KNN_BLOCK     256u      /* queries per workgroup, one per lane                                  */
+#define SLHIP_KNN_TILE      1024u     /* references per LDS tile (16 KiB)                                     */
+#define SLHIP_KNN_OUT_IDX   1u
+#define SLHIP_KNN_OUT_DIST2 2u
+#define SLHIP_KNN_OUT_COUNT 4u
+
+typedef struct {
+    uint32_t n_sets;           /* n                                                                           */
+    uint32_t n_queries;        /* Q >= 1 queries per set                                                      */
+    uint32_t n_refs;           /* R >= 1 references per set                                                   */
+    uint32_t query_stride;     /* points from one set's queries to the next set's, >= n_queries               */
+    uint32_t ref_stride;       /* the same of the references, >= n_refs                                       */
+    uint32_t k;                /* 1..SLHIP_KNN_K_MAX neighbours per query                                     */
+    float max_dist;            /* >= 0, +inf: no gate; rule 3                                                 */
+    uint32_t skip_same;        /* 0 or 1: rule 3; 1 needs queries == refs and query_stride == ref_stride      */
+    uint32_t outputs;          /* SLHIP_KNN_OUT_* bits, at least one                                          */
+    uint32_t _pad[3];
+} slhip_point_knn_params; /* 48 bytes */
+
+typedef struct {               /* read only when its bit is set; every pointer 4-byte aligned                 */
+    int32_t* idx;              /* i32 [n, Q, k], -1 in an empty slot                                          */
+    float* dist2;              /* f32 [n, Q, k], NaN in an empty slot                                         */
+    int32_t* count;            /* i32 [n, Q]                                                                  */
+} slhip_point_knn_out;
+
+/* Every rule of the record, in the order of its fields, then the two bounds above.  A negative error with
+ * slhip_last_error text.  No device. */
+int slhip_point_knn_check_params(const slhip_point_knn_params* params);
+/* d_queries f32 [n, query_stride, 4] and d_refs f32 [n, ref_stride, 4] (the layout of the point sets' camera and coord
+ * outputs), both 16-byte aligned; they may be the same pointer (a self-search), and must be with skip_same.  Every output
+ * named in params->outputs is written for every query, the others are not touched.  n_sets == 0 does nothing; null pointers
+ * (an output named in the mask included), misalignment and bad parameters are refused before anything touches the device.
+ * One workgroup of 256 lanes per set and 256 queries, the references through LDS in tiles of SLHIP_KNN_TILE; k = 1 is the
+ * same kernel.  Asynchronous on `stream`.                                                                                 */
+int slhip_point_knn(const slhip_point_knn_params* params, const float* d_queries, const float* d_refs,
+                    const slhip_point_knn_out* out, void* stream);
+/* The plain scan of rule 4 on host arrays through csrc/slhip_knn_rules.h.  Host only, no device: the handle the CPU tests use. */
+int slhip_point_knn_host(const slhip_point_knn_params* params, const float* h_queries, const float* h_refs,
+                         const slhip_point_knn_out* out);
+/* Developer hook (tools/time_point_knn.py): HIP events round the last slhip_point_knn [0] (-1: not run). */
+int slhip_point_knn_timing_enable(int on);
+int slhip_point_knn_timings(float ms_out[1]);
+
 /* bp_to_vertices_and_colors (diff.py:215-352, row D6), dense form: for every pixel that belongs to one
  * of the n_obj objects, the negated gradient of the objective w.r.t. the three vertices of its triangle
  * (-bary_k * dL/dX, X = object coordinates of the pixel) and w.r.t. their colours (-bary_k * dL/dI).

@@ -20,6 +20,7 @@ from stillleben_amd import pose_fit, PoseFit  # noqa: F401  (additive: the pose 
 from stillleben_amd import pose_align, PoseAlign  # noqa: F401  (additive: the robust pose of every set of 3D-3D correspondences)
 from stillleben_amd import pose_icp, PoseICP  # noqa: F401  (additive: ICP refinement of a pose against the depth's camera points)
 from stillleben_amd import render_flow, RenderFlow  # noqa: F401  (additive: optical flow, scene flow and occlusion between two renders)
+from stillleben_amd import point_knn, PointNeighbours, PointPyramid  # noqa: F401  (additive: k nearest neighbours between point sets)
 
 __all__ = _impl.__all__
 for _name in ("camera_model", "diff", "extension", "losses", "profiling"):

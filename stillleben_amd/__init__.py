@@ -52,6 +52,8 @@ from . import pose_icp  # noqa: F401  (additive: ICP refinement of a pose agains
 from .pose_icp import PoseICP  # noqa: F401
 from . import render_flow  # noqa: F401  (additive: optical flow, scene flow and occlusion between two renders of a scene)
 from .render_flow import RenderFlow  # noqa: F401
+from . import point_knn  # noqa: F401  (additive: the k nearest neighbours between point sets and the RandLA pyramid)
+from .point_knn import PointNeighbours, PointPyramid  # noqa: F401
 
 __all__ = [
     'init', 'init_cuda', 'render_debug_image', 'Animator', 'ImageLoader', 'ImageSaver', 'LightMap',
@@ -69,6 +71,7 @@ __all__ = [
     'pose_align', 'PoseAlign',
     'pose_icp', 'PoseICP',
     'render_flow', 'RenderFlow',
+    'point_knn', 'PointNeighbours', 'PointPyramid',
 ]
 
 

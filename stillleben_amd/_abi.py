@@ -81,6 +81,8 @@ FLOW_SLOTS_MAX = 256                                                   # SLHIP_F
 FLOW_VALID, FLOW_INSIDE, FLOW_VISIBLE = 1, 2, 4                        # SLHIP_FLOW_*: the flag bits of a pixel of the render flow
 FLOW_OUT_FLOW, FLOW_OUT_SCENE, FLOW_OUT_FLAGS, FLOW_OUT_COUNTS = 1, 2, 4, 8      # SLHIP_FLOW_OUT_*
 FLOW_MATCH_INSTANCE = 1                                                # SLHIP_FLOW_MATCH_INSTANCE (params.flags)
+KNN_K_MAX, KNN_BLOCK, KNN_TILE = 32, 256, 1024                         # SLHIP_KNN_K_MAX, SLHIP_KNN_BLOCK, SLHIP_KNN_TILE
+KNN_OUT_IDX, KNN_OUT_DIST2, KNN_OUT_COUNT = 1, 2, 4                    # SLHIP_KNN_OUT_*
 ABI_VERSION = 5
 DEFAULT_HULL_PAIRS, DEFAULT_CONTACTS = 2048, 1024   # SLHIP_DEFAULT_HULL_PAIRS / SLHIP_DEFAULT_CONTACTS of include/slhip.h
 COMM_ID_BYTES = 128
@@ -458,6 +460,20 @@ class PoseIcpOut(C.Structure):
                 ("nearest", C.c_void_p)]
 
 
+# slhip_point_knn_params (include/slhip.h), 48 bytes
+POINT_KNN_PARAMS_DTYPE = np.dtype([
+    ("n_sets", np.uint32), ("n_queries", np.uint32), ("n_refs", np.uint32), ("query_stride", np.uint32), ("ref_stride", np.uint32),
+    ("k", np.uint32), ("max_dist", np.float32), ("skip_same", np.uint32), ("outputs", np.uint32), ("_pad", np.uint32, (3,)),
+])
+assert POINT_KNN_PARAMS_DTYPE.itemsize == 48
+
+
+class PointKnnOut(C.Structure):
+    """slhip_point_knn_out: the output pointers of slhip_point_knn."""
+
+    _fields_ = [("idx", C.c_void_p), ("dist2", C.c_void_p), ("count", C.c_void_p)]
+
+
 # slhip_asset / slhip_synth_params / slhip_synth_object / slhip_synth_scene (include/slhip.h)
 ASSET_DTYPE = np.dtype([
     ("mesh_to_object", np.float32, (16,)), ("bbox_min", np.float32, (4,)), ("bbox_max", np.float32, (4,)),
@@ -743,6 +759,12 @@ def lib():
         L.slhip_render_flow_host.argtypes = L.slhip_render_flow.argtypes[:-1]
         L.slhip_render_flow_motion.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.slhip_render_flow_motion_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    if hasattr(L, "slhip_point_knn"):                # (absent from older builds selected through SLHIP_LIB for A/B runs)
+        L.slhip_point_knn_check_params.argtypes = [C.c_void_p]
+        L.slhip_point_knn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PointKnnOut), C.c_void_p]
+        L.slhip_point_knn_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PointKnnOut)]
+        L.slhip_point_knn_timing_enable.argtypes = [C.c_int]
+        L.slhip_point_knn_timings.argtypes = [C.POINTER(C.c_float * 1)]
     L.slhip_stream_create_cu_range.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.slhip_stream_destroy.argtypes = [C.c_void_p]
     L.slhip_synth_stage.argtypes = [C.c_void_p] * 8

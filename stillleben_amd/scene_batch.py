@@ -734,6 +734,23 @@ class SceneBatch:
             raise _abi.SlhipError(_device.no_cpu("pose_icp"))
         return pose_icp.solve(points.camera, init.contiguous(), asset[scene, slot].contiguous(), bank, **kw)
 
+    def point_graph(self, points, k=16, space="camera", **kw):
+        """sl.point_knn on the point sets of a render (`points` = what points(...) returned): the k nearest points of every
+        point within its own set, in the camera frame (`space="camera"`, the `camera` output) or the object frame
+        (`space="coord"`, the `coord` output).  Without `ratios=` a PointNeighbours (sl.point_knn.search; `kw`: max_dist,
+        skip_same, n_queries, n_refs, outputs); with `ratios=` the PointPyramid of every set (sl.point_knn.pyramid; `kw`:
+        ratios, interp).  A padded point (w == 0) has no neighbours and is nobody's neighbour."""
+        from . import point_knn
+
+        if space not in ("camera", "coord"):
+            raise ValueError("point_knn: `space` must be \"camera\" or \"coord\", not %r" % (space,))
+        cloud = getattr(points, space, None)
+        if cloud is None:
+            raise RuntimeError("point_knn: the ObjectPoints need their `%s` output" % space)
+        if "ratios" in kw:
+            return point_knn.pyramid(cloud, k=k, **kw)
+        return point_knn.search(cloud, k=k, **kw)
+
     # ---- host views (tests, inspection, hand-over to the per-scene API) ---------------------------------------
     def _host(self, t, dtype, count):
         return np.frombuffer(t.cpu().numpy().tobytes()[:count * dtype.itemsize], dtype=dtype).copy()
